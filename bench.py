@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — images/sec of the Qwen-Image DiT denoising path on N MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line; everything else this file can measure or
+check runs only with --full (below).  --dump-outputs DIR writes what the last timed step returned (see dump_outputs): the
+inputs depend on the arguments only, so two builds of the project can be compared output for output.
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment launches itself: the parent spawns N ranks of this
 file (env:// rendezvous on 127.0.0.1, one rank per GPU, same model as the reference's engine spawning one WorkerProc per
@@ -17,9 +21,13 @@ tile quantisation: 10 items = 163 row-tiles of 256, which fills the 256 CUs to 9
 the attention grid to 99.6 % (R=3: 92-98 % / 95.6 %; R=1: 77-93 %).  Inputs
 (seeded noise, synthetic prompt embeddings T=64, random-init bf16 weights of the real architecture) are resident
 in HBM before the timed region.  value = N*K*R images / max-over-ranks seconds.  Data-parallel by request
-(weak scaling): no collective inside the denoise loop.
+(weak scaling): no collective inside the denoise loop.  ms_per_step = milliseconds of one timed step (max over ranks).
 
-Also printed in the same JSON line:
+Every line also holds finite_outputs (the last step's images and latents are finite) and
+  per_rank     — every rank's wall seconds of the timed region and, from HIP events on its stream, the seconds it spent in the
+                 denoise loops, in the latent all-gather and in the VAE decodes (a sub-linear 1 -> N curve can be attributed).
+
+With --full, also printed in the same JSON line (--no-secondary / --no-engine / --no-cpu-baseline leave parts out):
   roofline     — dominant kernel = gemm_bf16_pp_kernel<GELU> (the ping-pong MFMA GEMM; MLP up-projection, 27 % of the DiT FLOPs, one shape
                  per launch so rocprofv3's per-kernel average is shape-pure): algorithmic 2*M*N*K flop per launch
                  / average launch duration measured here with HIP events on the launch stream.
@@ -30,8 +38,7 @@ Also printed in the same JSON line:
                  (256x256, 4 steps, batch 1) eager vs hipGraph replay, TeaCache rel_l1_thresh 0.2, and the SERVING path:
                  DiffusionEngine.submit / poll (a worker process running the continuous step batcher) fed 2R requests that
                  arrive staggered, against the static loop of the headline line.
-  per_rank     — every rank's wall seconds of the timed region and, from HIP events on its stream, the seconds it spent in the
-                 denoise loops, in the latent all-gather and in the VAE decodes (a sub-linear 1 -> N curve can be attributed).
+  collective   — (N > 1) proof that the all-gather carried every rank's latents: per-rank digests compared over a CPU group.
   --sp P       — (opt-in, needs --gpus P) after the headline measurement the P ranks form ONE Ulysses group and time a
                  single 2048x2048 true-CFG request sequence-parallel: `secondary.sp_*`; the 1-GPU value
                  of the same request is `secondary.res2048_bf16_ms_per_denoise_step` of an N = 1 run.
@@ -56,6 +63,30 @@ LAYERS = 60
 TRUE_CFG = 4.0
 PFLOP_PER_IMAGE = 2.777e15          # 40 x 69.310 TF (DiT) + 4.71 TF (VAE)
 PEAK_BF16 = 2.5e15                  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
+DUMP_BYTES = 64 * 10**6             # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(outdir: str, arrays: dict) -> dict:
+    """--dump-outputs: every array as float32 `<outdir>/<name>.npy`.  Smallest first, each array may use an equal share of what
+    the ones before it left of DUMP_BYTES; one larger than its share is written as `<name>_sample.npy` instead: its elements
+    (flattened, C order) at a fixed set of indices, drawn without replacement with seed 0 and sorted, so the same shapes always
+    give the same sample.  Returns {file name: shape written}."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    left, written = DUMP_BYTES, {}
+    order = sorted(arrays, key=lambda k: arrays[k].numel())
+    for i, name in enumerate(order):
+        a = arrays[name].detach().float().cpu().numpy()
+        cap = (left // (len(order) - i) - 4096) // 4         # float32 elements this array may use (4 KiB for the .npy header)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        path = os.path.join(outdir, name + ".npy")
+        np.save(path, np.ascontiguousarray(a, dtype=np.float32))
+        written[name + ".npy"] = list(a.shape)
+        left -= os.path.getsize(path)
+    return written
 
 
 def cpu_baseline(layers_sample: int = 4) -> dict:
@@ -550,9 +581,14 @@ def main():
     # R = 5: 2R = 10 items x 4160 rows gives 163 m-tiles: the N = 3072 GEMMs fill 7.64 -> 8 rounds of 256 CUs (95.5 %; R = 3:
     # 4.59 -> 5 rounds, 91.9 %), attention 15.94 -> 16 rounds.  Same box: R = 3 0.4232, R = 5 0.4325, R = 7 0.4323 images/s.
     ap.add_argument("--requests", type=int, default=5, help="requests step-batched per rank per step (R)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-engine", action="store_true", help="skip the serving-path (DiffusionEngine) secondary line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run the roofline launch, the secondary lines, the serving path, "
+                         "the CPU baseline and (N > 1) the gather proof; a plain run does only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's latents and images as float32 .npy files to DIR (rank 0; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary lines")
+    ap.add_argument("--no-engine", action="store_true", help="with --full: skip the serving-path (DiffusionEngine) secondary line")
     ap.add_argument("--sp", type=int, default=0, help="P = --gpus: also time one 2048^2 request Ulysses-parallel over all ranks")
     # dev / test only: run the N-rank control flow (self-launch, rendezvous, per-rank stats, gather, JSON) on ONE device —
     # every rank on device 0 over a gloo group (RCCL refuses duplicate GPUs).  tests/test_gpu_multirank_bench.py
@@ -564,6 +600,8 @@ def main():
     ap.add_argument("--dist-backend", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--share-device", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     from vllm_omni_amd.diffusion.data import OmniDiffusionConfig, TransformerConfig
     from vllm_omni_amd.diffusion.distributed import data_parallel as dp
@@ -667,13 +705,18 @@ def main():
                  "numa_node": int(t[5]), "numa_pinned": bool(t[6]), "host_cpus": int(t[7]), "device": int(t[8])}
                 for r, t in enumerate(allstats)]
     ok = bool(torch.isfinite(img.float()).all()) and bool(torch.isfinite(gathered.float()).all())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: every rank's finished latents (after the gather) and
+        # this rank's decoded images
+        dumped = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, {"latents": gathered, "images": img})}
 
-    # N > 1: make the record prove that the collective carried N ranks' data.  Every rank digests (a) the latents it contributed
-    # in the last step and (b) each rank-sized slice of what the all-gather returned to it; the digests travel over the CPU (gloo)
-    # group, and rank 0 checks that every rank received, in slot r, exactly what rank r sent (different seeds per rank: a gather
-    # that returned local data N times, or skipped a rank, cannot pass).
+    # N > 1 (--full): make the record prove that the collective carried N ranks' data.  Every rank digests (a) the latents it
+    # contributed in the last step and (b) each rank-sized slice of what the all-gather returned to it; the digests travel over the
+    # CPU (gloo) group, and rank 0 checks that every rank received, in slot r, exactly what rank r sent (different seeds per rank:
+    # a gather that returned local data N times, or skipped a rank, cannot pass).
     collective = None
-    if world > 1:
+    if world > 1 and args.full:
         def digest(t):                                     # order-sensitive 62-bit digest of the bf16 bits
             v = t.contiguous().view(torch.int16).to(torch.int64).flatten() & 0xFFFF
             w = (torch.arange(v.numel(), device=v.device, dtype=torch.int64) % 65521) + 1
@@ -742,9 +785,11 @@ def main():
             "finite_outputs": ok, "per_rank": per_rank,
             **({"collective": collective} if collective is not None else {}),
             "dit_mfma_roofline_frac": (value / world) * PFLOP_PER_IMAGE * (args.layers / LAYERS) / PEAK_BF16,
-            "roofline": measure_roofline(dev, R),
+            **({"outputs_dumped": dumped} if dumped is not None else {}),
         }
-        if world == 1 and not args.no_secondary:
+        if args.full:
+            line["roofline"] = measure_roofline(dev, R)
+        if args.full and world == 1 and not args.no_secondary:
             try:
                 line["secondary"] = secondary_lines(pipe, dev, R, args.layers)
             except Exception as e:  # noqa: BLE001 - the headline line must survive a failing secondary measurement
@@ -753,7 +798,7 @@ def main():
             line.setdefault("secondary", {}).update(sp_line)
     # the serving topology (N = 1 and N > 1): rank 0 drives a DiffusionEngine with one worker process per GPU; the ranks of the
     # static measurement release their weights first and (N > 1) wait on the CPU until rank 0 is through
-    run_engine = not args.no_engine and not args.sp
+    run_engine = args.full and not args.no_engine and not args.sp
     if run_engine:
         del pipe                                             # every worker process builds its own 41 GB of weights
         import gc
@@ -767,7 +812,7 @@ def main():
             devices = [r % torch.cuda.device_count() for r in range(world)] if args.share_device else None
             line.setdefault("secondary", {}).update(engine_line_guarded(R, args.layers, value, world, devices, args.dist_backend,
                                                                         args.engine_timeout))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if world > 1:

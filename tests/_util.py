@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite (oracle access, golden loading, error metrics)."""
+import glob
 import json
 import os
 
@@ -20,15 +21,24 @@ def cosine(a: torch.Tensor, b: torch.Tensor) -> float:
     return float(torch.dot(a, b) / (a.norm() * b.norm()))
 
 
+def _load_npz(name: str) -> dict:
+    """name.npz plus any name.part-<array>.npz next to it: a fixture over the 1 MiB limit of a committed file keeps some of its
+    arrays in such parts."""
+    z = dict(np.load(os.path.join(GOLDEN_DIR, name + ".npz")))
+    for part in sorted(glob.glob(os.path.join(glob.escape(GOLDEN_DIR), glob.escape(name) + ".part-*.npz"))):
+        z.update(np.load(part))
+    return z
+
+
 def load_golden(name: str):
-    z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+    z = _load_npz(name)
     meta = json.loads(str(z["meta"]))
     return z, meta, meta["case"]
 
 
 def load_golden_raw(name: str):
     """Fixtures whose meta has no 'case' entry (pipe_helpers)."""
-    z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+    z = _load_npz(name)
     meta = json.loads(str(z["meta"]))
     return z, meta, meta.get("case")
 

@@ -128,7 +128,7 @@ def test_batch_keys_are_served_round_robin():
         assert torch.equal(done[k].output, _solo(r)), k
 
 
-def test_engine_two_workers_dispatch_staggered_requests_and_rpc():
+def test_engine_two_workers_dispatch_staggered_requests_and_rpc(monkeypatch):
     """2 worker processes (gloo ranks), least-outstanding dispatch, requests submitted while others run, results equal
     solo runs, a failing request is isolated, broadcast RPC reaches every worker, clean shutdown."""
     import _fake_pipeline
@@ -136,6 +136,9 @@ def test_engine_two_workers_dispatch_staggered_requests_and_rpc():
     from vllm_omni_amd.diffusion.diffusion_engine import DiffusionEngine
     from vllm_omni_amd.diffusion.request import OmniDiffusionRequest
 
+    # the workers inherit this: host-only ranks also on a GPU machine (a visible GPU would make worker r take cuda:r over RCCL)
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "")
+    monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "")
     eng = DiffusionEngine(OmniDiffusionConfig(num_gpus=2, max_step_batch=3, dist_timeout=60),
                           pipeline_factory=_fake_pipeline.make, post_process_func=None, start_timeout_s=120)
     try:

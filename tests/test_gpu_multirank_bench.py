@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_two_ranks_on_one_device_over_gloo():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--layers", "2", "--steps", "1", "--warmup", "1",
-           "--requests", "2", "--no-cpu-baseline", "--dist-backend", "gloo", "--share-device"]
+           "--requests", "2", "--full", "--no-cpu-baseline", "--dist-backend", "gloo", "--share-device"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -44,15 +44,18 @@ def test_bench_two_ranks_on_one_device_over_gloo():
         assert w["steps"] > 0 and 0 < w["busy_frac"] <= 1.0 + 1e-6 and 1.0 <= w["mean_batch"] <= 2.0
 
 
-def test_bench_two_ranks_under_torch_distributed_run():
+def test_bench_two_ranks_under_torch_distributed_run(tmp_path):
     """The launcher the DRIVER uses for N > 1: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N ...` (ranks, local ranks and the rendezvous come from its environment, not from bench.py's own
-    self-launch) — on one device over gloo."""
+    self-launch) — on one device over gloo.  --dump-outputs: rank 0 writes both ranks' gathered latents and its own image."""
+    import numpy as np
+
     from test_host_logic import _free_port
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--layers", "1", "--steps", "1",
-           "--warmup", "1", "--requests", "1", "--no-cpu-baseline", "--no-engine", "--dist-backend", "gloo", "--share-device"]
+           "--warmup", "1", "--requests", "1", "--full", "--no-cpu-baseline", "--no-engine", "--dist-backend", "gloo",
+           "--share-device", "--dump-outputs", str(tmp_path / "out")]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -62,6 +65,10 @@ def test_bench_two_ranks_under_torch_distributed_run():
     assert j["n_gpus"] == 2 and j["config"]["parallelism"] == "dp2" and j["finite_outputs"]
     assert j["collective"]["world"] == 2 and j["collective"]["gathered_checksum_matches_all_ranks"]
     assert [r["rank"] for r in j["per_rank"]] == [0, 1]
+    lat, img = np.load(tmp_path / "out" / "latents.npy"), np.load(tmp_path / "out" / "images.npy")
+    assert lat.dtype == img.dtype == np.float32 and lat.shape == (2, 4096, 64) and img.shape == (1, 3, 1024, 1024)
+    assert np.isfinite(lat).all() and np.isfinite(img).all() and not np.array_equal(lat[0], lat[1])   # two ranks' seeds
+    assert j["outputs_dumped"]["files"] == {"latents.npy": [2, 4096, 64], "images.npy": [1, 3, 1024, 1024]}
 
 
 def test_bench_eight_ranks_on_one_device_over_gloo():
@@ -69,7 +76,7 @@ def test_bench_eight_ranks_on_one_device_over_gloo():
     max-over-ranks timing) on one device with one layer; the serving line is skipped (eight worker processes x their own weights
     add nothing the 2-rank test does not cover).  Reference spawn shape: vllm_omni/diffusion/diffusion_engine.py:211-270."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--layers", "1", "--steps", "1", "--warmup", "1",
-           "--requests", "1", "--no-cpu-baseline", "--no-engine", "--dist-backend", "gloo", "--share-device"]
+           "--requests", "1", "--full", "--no-cpu-baseline", "--no-engine", "--dist-backend", "gloo", "--share-device"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]

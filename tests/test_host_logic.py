@@ -264,8 +264,16 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _host_only_rank():
+    """A spawned CPU rank stays one on a GPU machine: no device visible and no HIP runtime started in it (GPUWorker and
+    init_distributed ask torch.cuda.is_available(); a visible GPU would make rank r take cuda:r over RCCL)."""
+    os.environ.update(HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    torch.cuda.is_available = lambda: False
+
+
 def _dp_worker(rank, world, port, q, fail_rank=-1, mixed=False, decode_fail_rank=-1, layered=False):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    _host_only_rank()
     sys.path.insert(0, ROOT)
     from vllm_omni_amd.diffusion.data import DiffusionOutput, OmniDiffusionConfig
     from vllm_omni_amd.diffusion.request import OmniDiffusionRequest
@@ -898,6 +906,30 @@ def test_bench_self_launch_reports_a_failing_rank_instead_of_hanging(tmp_path):
             "with bench._Watchdog(0.3, 'a test phase'):\n    time.sleep(5)\n" % ROOT)
     w = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert w.returncode == 3 and "still in 'a test phase'" in w.stderr
+
+
+def test_bench_dump_outputs_stay_within_budget_and_sample_the_same_elements(tmp_path):
+    """`bench.py --dump-outputs DIR` at the headline shapes (R = 5: latents [5, 4096, 64], images [5, 3, 1024, 1024] in bf16):
+    float32 files, at most 64 MB together; the array over its share is a sample at fixed flat indices, so two runs (two builds)
+    compare element for element."""
+    import sys
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    arrays = {"latents": torch.randn(5, 4096, 64, generator=g).bfloat16(), "images": torch.rand(5, 3, 1024, 1024, generator=g).bfloat16()}
+    a = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert set(a) == {"latents.npy", "images_sample.npy"} and a["latents.npy"] == [5, 4096, 64]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in a) <= bench.DUMP_BYTES
+    lat = np.load(tmp_path / "a" / "latents.npy")
+    assert lat.dtype == np.float32 and np.array_equal(lat, arrays["latents"].float().numpy())
+    smp = np.load(tmp_path / "a" / "images_sample.npy")
+    assert smp.dtype == np.float32 and smp.size > 14_000_000                                  # what the latents left of the budget
+    full = arrays["images"].float().numpy().reshape(-1)                                      # the documented indices: seed 0, sorted
+    assert np.array_equal(smp, full[np.sort(np.random.default_rng(0).choice(full.size, smp.size, replace=False))])
+    bench.dump_outputs(str(tmp_path / "b"), {k: v.clone() for k, v in arrays.items()})
+    assert np.array_equal(np.load(tmp_path / "b" / "images_sample.npy"), smp)                 # the same indices every run
 
 
 def test_bench_engine_line_runs_in_a_guarded_child_process_group():

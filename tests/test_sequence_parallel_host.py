@@ -155,6 +155,9 @@ def test_sp_driver_pipelines_generators_over_gloo(world):
 def _sp_worker_rank(rank, world, port, q, degree):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     sys.path.insert(0, ROOT)
+    from test_host_logic import _host_only_rank
+
+    _host_only_rank()
     import torch.distributed as dist
 
     from vllm_omni_amd.diffusion.data import DiffusionOutput, DiffusionParallelConfig, OmniDiffusionConfig
