@@ -306,7 +306,7 @@ int omni_rope_interleaved(const omni_bf16* x, omni_bf16* y, int32_t B, int32_t S
 /* ------------------------------------------------------------------------------------------------
  * Flash attention forward, non-causal, no mask, head_dim 128, bf16 in/out, fp32 softmax/accumulate.
  * Replaces F.scaled_dot_product_attention at vllm_omni/diffusion/attention/backends/sdpa.py:46-66
- * (and flash_attn_func / sageattn in the sibling backends).
+ * (and flash_attn_func in the flash_attn sibling backend; the int8 `sageattn` of sage_attn.py is omni_attn_params.qk_int8).
  * q,k,v,out: [total_rows, H*128] with row strides ld* (the reference's [B,S,H,dh] "NHD" layout
  * flattened over B,S); item b owns rows [cu_seqlens[b], cu_seqlens[b+1]).  cu_seqlens is a
  * DEVICE int32 array of B+1 entries.  max_seqlen bounds the grid.
@@ -360,8 +360,27 @@ typedef struct {
   const void* mask;
   int32_t mask_type;                   /* 0 none, 1 bool bytes, 2 bf16 additive, 3 fp32 additive */
   int64_t mask_stride_b, mask_stride_h, mask_stride_q, mask_stride_k;
+  /* ABI v14 — appended; all zero = the bf16 kernel above, bit for bit.
+   * qk_int8 = 1: SAGE_ATTN (the reference's sage_attn.py backend, SageAttention v1: int8 Q K^T, fp32 softmax, bf16 P V), per item
+   * and head: km = mean of the item's key rows (fp32); k' = k - km (softmax unchanged); q *= softmax_scale * log2(e); per block
+   * of 64 rows from the item's first row, q and k' are quantised to int8 with scale amax|x| / 127 (all-zero block: 1), round to
+   * nearest even; s = float(q8 . k8^T) * sq * sk; exp2-domain online softmax in fp32; P rounded to bf16; bf16 P V with an fp32
+   * accumulator.  No mask, not causal (OMNI_ERR_UNSUPPORTED), head_dim 64 or 128; `workspace` (16-byte aligned DEVICE memory of
+   * at least omni_attn_quant_workspace_bytes(p) bytes) receives the int8 q / k, the block scales and the key means
+   * (OMNI_ERR_BAD_ARG when missing or short).  out_k32_rows = R > 0 (qk_int8 only): out is K32-blocked [H * dh / 32][R][32]
+   * over the R rows of the whole buffer (ldo ignored), as omni_flash_attn_fwd_ex; R must cover cu_seqlens_q[B] (query rows at or
+   * past R are not written).  item_skip (nullable DEVICE int32 [B], qk_int8 only): item b with item_skip[b] != 0 costs nothing
+   * and its output rows are left untouched (the TeaCache predicate of omni_dit_forward). */
+  int32_t qk_int8;
+  int32_t out_k32_rows;
+  void* workspace;
+  size_t workspace_bytes;
+  const int32_t* item_skip;
 } omni_attn_params;
 int omni_flash_attn_general(const omni_attn_params* p, omni_stream stream);
+/* ABI v14 — bytes of the qk_int8 workspace for these bounds (B, H, H_kv, head_dim, max_seqlen_q, max_seqlen_k); 0 for
+ * parameters qk_int8 does not take. */
+size_t omni_attn_quant_workspace_bytes(const omni_attn_params* p);
 
 /* ------------------------------------------------------------------------------------------------
  * Small-batch weight-streaming linear:  y[b, n] = act_out( sum_k act_in(x[b, k]) * W[n, k] + bias[n] ).
@@ -541,6 +560,11 @@ typedef struct {
   const int32_t* txt_joint_row;   /* [n_txt_rows] -> joint row                           */
   const int32_t* joint_pos;       /* [n_joint_rows] -> rope table row                    */
   int32_t txt_pos_end;            /* rope rows < this are text positions                 */
+  int32_t attn_qk_int8;           /* ABI v14.  NOT appended at the end: it occupies the former padding behind txt_pos_end, so
+                                   * the descriptor keeps its size and every other offset (a caller built against v13 that
+                                   * zero-initialises the struct gets 0 here).  1 = the joint attention of every block runs as
+                                   * omni_attn_params.qk_int8 (SAGE_ATTN) on q / k / v of the block; its int8 copies live in
+                                   * the MLP hidden buffer of the workspace, dead during the attention (same workspace size) */
   const omni_bf16 *rope_cos, *rope_sin; /* [npos, 64] bf16                               */
   omni_bf16* noise_pred;          /* [n_img_rows, out_channels_packed]                   */
   /* workspace (caller-allocated, sizes from omni_dit_workspace_bytes) */

@@ -12,7 +12,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libomni_cdna4.so")   # fixed: dev sweeps assign this attribute (tools/devlib.py)
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 c_bf16_p = C.c_void_p  # device pointer to uint16_t bf16 bits
 c_i32_p = C.c_void_p
@@ -78,6 +78,8 @@ class AttnParams(C.Structure):
         ("softmax_scale", C.c_float), ("causal", C.c_int32),
         ("mask", C.c_void_p), ("mask_type", C.c_int32),
         ("mask_stride_b", C.c_int64), ("mask_stride_h", C.c_int64), ("mask_stride_q", C.c_int64), ("mask_stride_k", C.c_int64),
+        ("qk_int8", C.c_int32), ("out_k32_rows", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),  # ABI v14
+        ("item_skip", c_i32_p),
     ]
 
 
@@ -144,7 +146,7 @@ class DitBatch(C.Structure):
         ("latents", c_bf16_p), ("prompt_embeds", c_bf16_p), ("timestep", c_f32_p),
         ("cu_seqlens", c_i32_p), ("img_item", c_i32_p), ("txt_item", c_i32_p),
         ("img_joint_row", c_i32_p), ("txt_joint_row", c_i32_p), ("joint_pos", c_i32_p),
-        ("txt_pos_end", C.c_int32),
+        ("txt_pos_end", C.c_int32), ("attn_qk_int8", C.c_int32),       # attn_qk_int8: ABI v14, former padding
         ("rope_cos", c_bf16_p), ("rope_sin", c_bf16_p),
         ("noise_pred", c_bf16_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
@@ -191,6 +193,7 @@ PROTOTYPES = {
                                          C.c_int64, c_i32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                          C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),         # ABI v11
     "omni_flash_attn_general": (C.c_int, [C.POINTER(AttnParams), C.c_void_p]),                      # ABI v11
+    "omni_attn_quant_workspace_bytes": (C.c_size_t, [C.POINTER(AttnParams)]),                        # ABI v14
     "omni_linear_smallbatch": (C.c_int, [c_bf16_p, C.c_int64, C.c_int32, c_bf16_p, c_bf16_p, C.c_int64, C.c_int32,
                                          c_bf16_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "omni_timestep_sinusoid": (C.c_int, [c_f32_p, C.c_int32, C.c_int32, C.c_float, c_bf16_p, C.c_void_p]),

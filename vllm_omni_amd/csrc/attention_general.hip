@@ -288,11 +288,16 @@ extern "C" int omni_flash_attn_general(const omni_attn_params* p, omni_stream st
   if (p->causal != 0 && p->causal != 1) return OMNI_ERR_BAD_ARG;
   if (p->mask_type < 0 || p->mask_type > 3 || (p->mask_type != 0) != (p->mask != nullptr)) return OMNI_ERR_BAD_ARG;
   if (p->head_dim != 64 && p->head_dim != 128) return OMNI_ERR_UNSUPPORTED;
+  if (p->qk_int8 != 0 && p->qk_int8 != 1) return OMNI_ERR_BAD_ARG;
+  if (p->out_k32_rows < 0) return OMNI_ERR_BAD_ARG;
+  if (p->qk_int8 == 1 && (p->mask_type != 0 || p->causal)) return OMNI_ERR_UNSUPPORTED;
+  if (p->qk_int8 == 0 && (p->out_k32_rows != 0 || p->item_skip)) return OMNI_ERR_UNSUPPORTED;   // the int8 path's options
   if (!omni_aligned16(p->q) || !omni_aligned16(p->k) || !omni_aligned16(p->v) || (reinterpret_cast<uintptr_t>(p->out) & 7) ||
       (p->ldq % 8) || (p->ldk % 8) || (p->ldv % 8) || (p->ldo % 4))
     return OMNI_ERR_ALIGN;
   if (p->mask_type == 2 && (reinterpret_cast<uintptr_t>(p->mask) & 1)) return OMNI_ERR_ALIGN;
   if (p->mask_type == 3 && (reinterpret_cast<uintptr_t>(p->mask) & 3)) return OMNI_ERR_ALIGN;
+  if (p->qk_int8 == 1) return omni_internal_sage_attn(p, p->item_skip, 0, stream);     // SAGE_ATTN: attention_sage.hip
   hipStream_t s = static_cast<hipStream_t>(stream);
   return p->head_dim == 128 ? launch_general<128>(p, s) : launch_general<64>(p, s);
 }

@@ -163,6 +163,9 @@ int omni_internal_flash_attn(const omni_bf16* q, const omni_bf16* k, const omni_
                              int64_t ldk, int64_t ldv, int64_t ldo, const int32_t* cu_seqlens, int32_t B, int32_t H,
                              int32_t head_dim, int32_t max_seqlen, float softmax_scale, int32_t out_k32_rows,
                              const int32_t* item_skip, int32_t q_prescaled, void* part_ws, size_t part_ws_bytes, void* stream);
+// internal: SAGE_ATTN (attention_sage.hip) — omni_flash_attn_general's qk_int8 path with a per-item device skip predicate and
+// q_prescaled = 1 for a q that already carries softmax_scale * log2(e); workspace / alignment checked here, the rest by the caller
+int omni_internal_sage_attn(const omni_attn_params* p, const int32_t* item_skip, int32_t q_prescaled, void* stream);
 // internal: TeaCache device-side decision / residual kernels (elementwise.hip), used by omni_dit_forward
 int omni_internal_teacache_decide(const omni_teacache* tc, const omni_bf16* mod, int32_t n_items, int32_t rows_per_item,
                                   int32_t n_img_rows, int32_t n_txt_rows, int32_t D, int32_t blocked, void* stream);

@@ -177,6 +177,7 @@ int run_block(const omni_dit_weights* w, int l, const omni_dit_batch* b, const W
               BlockPhase phase = BLOCK_ALL, const omni_bf16* attn_in = nullptr, PendingFinish* pend = nullptr,
               bool may_defer_down = false) {
   const omni_dit_layer_weights& L = w->layers[l];
+  if (b->attn_qk_int8 != 0 && b->attn_qk_int8 != 1) return OMNI_ERR_BAD_ARG;
   const int32_t Ri = b->n_img_rows, Rt = b->n_txt_rows, nT = b->n_temb;
   const int32_t D = w->num_heads * w->head_dim;
   const float eps = 1e-6f;
@@ -283,7 +284,21 @@ int run_block(const omni_dit_weights* w, int l, const omni_dit_batch* b, const W
                                b->joint_pos, b->txt_pos_end, eps, stream));
   }
   if (phase == BLOCK_QKV) return OMNI_OK;
-  // joint attention (reference :437-443 -> attention/backends/sdpa.py:46-66)
+  // joint attention (reference :437-443 -> attention/backends/sdpa.py:46-66); attn_qk_int8: SAGE_ATTN (sage_attn.py), its
+  // int8 q / k, scales and key means in the MLP hidden buffer — dead between the previous block's MLP-down and this block's MLP-up
+  if (b->attn_qk_int8) {
+    omni_attn_params ap = {};
+    ap.q = ws.q; ap.k = ws.k; ap.v = ws.v; ap.out = ws.attn;
+    ap.ldq = ap.ldk = ap.ldv = ap.ldo = D;
+    ap.cu_seqlens_q = ap.cu_seqlens_k = b->cu_seqlens;
+    ap.B = b->n_items; ap.H = ap.H_kv = w->num_heads; ap.head_dim = w->head_dim;
+    ap.max_seqlen_q = ap.max_seqlen_k = b->max_seqlen;
+    ap.softmax_scale = sm_scale; ap.qk_int8 = 1; ap.out_k32_rows = bRj;
+    ap.workspace = ws.mlp_h; ap.workspace_bytes = (size_t)(Ri + Rt) * 4 * D * sizeof(omni_bf16);
+    if (w->head_dim != 64 && w->head_dim != 128) return OMNI_ERR_UNSUPPORTED;
+    if (omni_attn_quant_workspace_bytes(&ap) > ap.workspace_bytes) return OMNI_ERR_UNSUPPORTED;
+    OMNI_TRY(omni_internal_sage_attn(&ap, pr.item, q_prescale ? 1 : 0, stream));
+  } else
   OMNI_TRY(omni_internal_flash_attn(ws.q, ws.k, ws.v, ws.attn, D, D, D, D, b->cu_seqlens, b->n_items, w->num_heads,
                                     w->head_dim, b->max_seqlen, sm_scale, bRj, pr.item, q_prescale ? 1 : 0, ws.attn_part,
                                     ws.attn_part_bytes, stream));
@@ -410,7 +425,7 @@ int prepare_positions(const omni_dit_batch* b, const Workspace& ws, omni_stream 
 }
 }  // namespace
 
-extern "C" int omni_abi_version(void) { return 13; }
+extern "C" int omni_abi_version(void) { return 14; }
 extern "C" const char* omni_build_arch(void) { return "gfx950"; }
 extern "C" const char* omni_status_string(int status) {
   switch (status) {

@@ -1,6 +1,7 @@
 """Backend selection — mirror of vllm_omni/diffusion/attention/selector.py:18-77.
 
-Same env var (DIFFUSION_ATTENTION_BACKEND) and the same `{name: {module, class}}` registry shape; CDNA4_FLASH is the default
+Same env var (DIFFUSION_ATTENTION_BACKEND) and the same `{name: {module, class}}` registry shape (CDNA4_FLASH, TORCH_SDPA and the
+reference's SAGE_ATTN); CDNA4_FLASH is the default
 wherever a GPU is visible; TORCH_SDPA (the reference's default) serves CPU-only hosts and explicit requests.  Unknown names raise ValueError like the reference.
 """
 import importlib
@@ -12,6 +13,8 @@ from .backends.abstract import AttentionBackend
 _BACKEND_CONFIG = {
     "CDNA4_FLASH": {"module": "vllm_omni_amd.diffusion.attention.backends.cdna4_flash", "class": "CDNA4FlashBackend"},
     "TORCH_SDPA": {"module": "vllm_omni_amd.diffusion.attention.backends.sdpa", "class": "SDPABackend"},
+    # int8 Q K^T (SageAttention v1) in HIP; opt-in only, never the default (backends/sage_attn.py)
+    "SAGE_ATTN": {"module": "vllm_omni_amd.diffusion.attention.backends.sage_attn", "class": "SageAttentionBackend"},
 }
 
 

@@ -337,6 +337,8 @@ class QwenImageTransformer2DModel(nn.Module):
         self.fp8 = False           # enable_fp8(): the block GEMMs run on e4m3 copies of their weights (BASELINE config 5)
         self._fp8_classes = frozenset()
         self._workspace = None
+        self._qk_int8 = None                # SAGE_ATTN selected? decided at the first forward (_attn_qk_int8)
+        self._sage_ws = None                # the sequence-parallel path's int8 attention workspace
         self._batch_cache: dict = {}
         self._mod_tables: dict = {}   # modulation_table_for_schedule(): (weights generation, sigmas, t_cond) -> table, newest last
 
@@ -548,6 +550,20 @@ class QwenImageTransformer2DModel(nn.Module):
         self._batch_cache[key] = ent
         return ent
 
+    def _attn_qk_int8(self) -> bool:
+        """The attention backend selector, consulted once (reference attention/layer.py:32 does it per layer at construction).
+        The native blocks never go through a plug-in AttentionImpl; the one selector outcome they act on is SAGE_ATTN, which
+        switches their joint attention to the int8 kernels (omni_dit_batch.attn_qk_int8).  Any other setting keeps the bf16
+        kernels exactly as before, so the selector is only asked when that name is set."""
+        if self._qk_int8 is None:
+            import os
+
+            from ...attention.selector import get_attn_backend
+
+            name = os.environ.get("DIFFUSION_ATTENTION_BACKEND")
+            self._qk_int8 = name is not None and name.upper() == "SAGE_ATTN" and get_attn_backend(-1).get_name() == "SAGE_ATTN"
+        return self._qk_int8
+
     def _descriptor(self, prepared: dict, rows_img: int, rows_txt: int) -> tuple:
         """DitBatch with the batch maps, RoPE tables and workspace filled in (the caller adds its tensors)."""
         rb: RaggedBatch = prepared["batch"]
@@ -567,6 +583,7 @@ class QwenImageTransformer2DModel(nn.Module):
         b.joint_pos, b.txt_pos_end = m["joint_pos"].data_ptr(), rb.txt_pos_end
         b.rope_cos, b.rope_sin = prepared["cos"].data_ptr(), prepared["sin"].data_ptr()
         b.workspace, b.workspace_bytes = self._workspace.data_ptr(), self._workspace.numel()
+        b.attn_qk_int8 = int(self._attn_qk_int8())
         return lib, w, b
 
     def forward_ragged(self, prepared: dict, latents: torch.Tensor, prompt_embeds: torch.Tensor,
@@ -750,7 +767,14 @@ class QwenImageTransformer2DModel(nn.Module):
                 recv = yield ("all_to_all", send)                            # [P(source = sequence chunk), 3, S_loc, Hh*d]
                 img_qkv = recv.permute(1, 0, 2, 3).reshape(3, S, Hh * d)
                 full = torch.cat([txt_qkv, img_qkv], dim=1).contiguous()     # [3, T + S, Hh*d]
-                o = ops.flash_attn_varlen(full[0], full[1], full[2], cu, Hh, T + S, scale)           # [T + S, Hh*d]
+                if self._attn_qk_int8():
+                    need = ops.attn_quant_workspace_bytes(1, Hh, Hh, d, T + S, T + S)
+                    if self._sage_ws is None or self._sage_ws.numel() < need:
+                        self._sage_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                    o = ops.flash_attn_general(full[0], full[1], full[2], cu, cu, Hh, Hh, T + S, T + S, scale, qk_int8=True,
+                                               workspace=self._sage_ws)
+                else:
+                    o = ops.flash_attn_varlen(full[0], full[1], full[2], cu, Hh, T + S, scale)           # [T + S, Hh*d]
                 send2 = torch.cat([o[T:].view(P, S_loc, Hh * d), o[:T].unsqueeze(0).expand(P, T, Hh * d)], dim=1).contiguous()
                 recv2 = yield ("all_to_all", send2)                          # [P(source = head slice), S_loc + T, Hh*d]
                 loc = recv2.permute(1, 0, 2).reshape(S_loc + T, D)           # heads in source-rank order = original order

@@ -316,10 +316,16 @@ _MASK_TYPES = {torch.bool: 1, torch.uint8: 1, torch.bfloat16: 2, torch.float32: 
 
 def flash_attn_general(q, k, v, cu_seqlens_q, cu_seqlens_k, num_heads: int, num_kv_heads: int, max_seqlen_q: int,
                        max_seqlen_k: int, softmax_scale: float, causal: bool = False, mask: torch.Tensor | None = None,
-                       mask_strides: tuple[int, int, int, int] | None = None, out=None):
+                       mask_strides: tuple[int, int, int, int] | None = None, out=None, *, qk_int8: bool = False,
+                       workspace: torch.Tensor | None = None, out_k32_blocked: bool = False,
+                       item_skip: torch.Tensor | None = None):
     """omni_flash_attn_general (ABI v11): q / out [rows_q, H * dh], k / v [rows_k, H_kv * dh], dh 64 or 128; per-item row ranges
     from the two int32 prefix-sum vectors.  `mask`: bool / uint8 (True = attend), bf16 or fp32 (additive) DEVICE tensor whose
-    element (b, h, i, j) sits `mask_strides` (in elements, 0 = broadcast) apart — `mask.expand(B, H, Sq, Sk).stride()`."""
+    element (b, h, i, j) sits `mask_strides` (in elements, 0 = broadcast) apart — `mask.expand(B, H, Sq, Sk).stride()`.
+    `qk_int8` (ABI v14): SAGE_ATTN — int8 Q K^T with smoothed K (include/omni_cdna4.h omni_attn_params.qk_int8); no mask, not
+    causal.  Its device workspace is `workspace` (uint8, at least attn_quant_workspace_bytes(...) bytes) or allocated here.
+    `out_k32_blocked` (int8 path only): out holds the K32-blocked order [H*dh/32][rows][32].  `item_skip` (int8 path only):
+    int32 DEVICE [B]; items with a non-zero entry are not computed and their output rows are left as they are."""
     rows, HD, ldq = _rows2d(q, "q")
     o = torch.empty(rows, HD, dtype=BF16, device=q.device) if out is None else out
     p = N.AttnParams()
@@ -338,8 +344,30 @@ def flash_attn_general(q, k, v, cu_seqlens_q, cu_seqlens_k, num_heads: int, num_
             raise N.OmniNativeError("mask_strides = the four element strides of the mask over (B, H, S_q, S_k)")
         p.mask, p.mask_type = mask.data_ptr(), _MASK_TYPES[mask.dtype]
         p.mask_stride_b, p.mask_stride_h, p.mask_stride_q, p.mask_stride_k = (int(x) for x in mask_strides)
+    if qk_int8:
+        p.qk_int8 = 1
+        p.out_k32_rows = rows if out_k32_blocked else 0
+        need = int(N.lib().omni_attn_quant_workspace_bytes(C.byref(p)))
+        if workspace is None:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device)
+        if not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+            raise N.OmniNativeError("the qk_int8 workspace must be a contiguous uint8 DEVICE tensor")
+        p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel()
+        if item_skip is not None:
+            p.item_skip = _p(item_skip, torch.int32, "item_skip")
+    elif out_k32_blocked or item_skip is not None:
+        raise N.OmniNativeError("out_k32_blocked and item_skip are options of the qk_int8 path")
     N.check(N.lib().omni_flash_attn_general(C.byref(p), _stream()), "omni_flash_attn_general")
     return o
+
+
+def attn_quant_workspace_bytes(B: int, num_heads: int, num_kv_heads: int, head_dim: int, max_seqlen_q: int,
+                               max_seqlen_k: int) -> int:
+    """omni_attn_quant_workspace_bytes: bytes of the qk_int8 (SAGE_ATTN) workspace for these bounds (0: not supported)."""
+    p = N.AttnParams()
+    p.B, p.H, p.H_kv, p.head_dim, p.max_seqlen_q, p.max_seqlen_k = B, num_heads, num_kv_heads, head_dim, max_seqlen_q, max_seqlen_k
+    p.qk_int8 = 1
+    return int(N.lib().omni_attn_quant_workspace_bytes(C.byref(p)))
 
 
 def linear_smallbatch(x, w, bias=None, act_in: int = 0, act_out: int = 0, out=None):
