@@ -147,7 +147,7 @@ __global__ __launch_bounds__(NW * 64, ((NW == 4 && NQ == 1) ? 2 : 1)) void flash
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
     uint16_t* __restrict__ out, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
     const int32_t* __restrict__ cu_seqlens, int n_heads_total, int H, float scale_log2e, int out_k32_rows,
-    int block_order, const int32_t* __restrict__ item_skip, int q_prescaled) {
+    int block_order, const int32_t* __restrict__ item_skip, int q_prescaled, int compact_B) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -170,11 +170,20 @@ __global__ __launch_bounds__(NW * 64, ((NW == 4 && NQ == 1) ? 2 : 1)) void flash
     hb = blockIdx.x % n_heads_total;
     qb = blockIdx.x / n_heads_total;
   }
-  const int b = hb / H, h = hb - b * H;
+  constexpr int QBLK = 32 * NW * NQ;
+  // compact grid (common.h omni_attn_compact_slots; compact_B = number of items, 0 = legacy): the list is (head, slot), the host
+  // passed n_heads_total = H, so hb is the head and qb the slot
+  int b, h;
+  if (compact_B) {
+    h = hb;
+    if (!omni_attn_slot_lookup(cu_seqlens, compact_B, QBLK, qb, b, qb)) return;
+  } else {
+    b = hb / H;
+    h = hb - b * H;
+  }
   if (item_skip && item_skip[b]) return;          // device-side predicate: this item's block stack is skipped (omni_teacache)
   const int seq_start = cu_seqlens[b];
   const int seq_len = cu_seqlens[b + 1] - seq_start;
-  constexpr int QBLK = 32 * NW * NQ;
   constexpr int NPIECE = 16 / NW;   // DMA pieces (1 KiB) per wave per operand per tile
   static_assert(!PP || (NW == 8 && NQ == 1), "ping-pong: 8 waves (2 DMA pieces per wave and operand: the counted vmcnt(2))");
   if (qb * QBLK >= seq_len) return;
@@ -657,7 +666,8 @@ int attn_pipe_waves(int n_heads_total, int max_seqlen) {
 template <int NW, int NQ = 1, int PP = 0>
 int launch_pipe(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, omni_bf16* out, int64_t ldq, int64_t ldk,
                 int64_t ldv, int64_t ldo, const int32_t* cu_seqlens, int32_t B, int32_t H, int32_t max_seqlen,
-                float softmax_scale, int out_k32_rows, hipStream_t s, const int32_t* item_skip = nullptr, int q_prescaled = 0) {
+                float softmax_scale, int out_k32_rows, hipStream_t s, const int32_t* item_skip = nullptr, int q_prescaled = 0,
+                int64_t total_rows = 0) {
   static std::atomic<uint64_t> attr_done{0};     // per device (common.h omni_once_per_device)
   OMNI_TRY_STATUS(omni_once_per_device(attr_done, [] {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_pipe_kernel<NW, NQ, PP>),
@@ -665,9 +675,17 @@ int launch_pipe(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, omni
   }));
   const int qblocks = (max_seqlen + 32 * NW * NQ - 1) / (32 * NW * NQ);
   const int nh = B * H;
+  // items of unequal length: the compact head-major slot grid where it is smaller (common.h: the rule and why)
+  if (const int slots = omni_attn_compact_slots(total_rows, B, max_seqlen, 32 * NW * NQ)) {
+    hipLaunchKernelGGL((flash_attn_fwd_pipe_kernel<NW, NQ, PP>), dim3(H * slots), dim3(NW * 64), LDS_BYTES, s, q, k, v, out, ldq,
+                       ldk, ldv, ldo, cu_seqlens, H, H, softmax_scale * 1.4426950408889634f, out_k32_rows, attn_block_order(),
+                       item_skip, q_prescaled, B);
+    OMNI_CHECK_LAUNCH();
+    return OMNI_OK;
+  }
   hipLaunchKernelGGL((flash_attn_fwd_pipe_kernel<NW, NQ, PP>), dim3(nh * qblocks), dim3(NW * 64), LDS_BYTES, s, q, k, v, out, ldq,
                      ldk, ldv, ldo, cu_seqlens, nh, H, softmax_scale * 1.4426950408889634f, out_k32_rows, attn_block_order(), item_skip,
-                     q_prescaled);
+                     q_prescaled, 0);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }
@@ -684,7 +702,8 @@ int launch_pipe(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, omni
 int omni_internal_flash_attn(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, omni_bf16* out, int64_t ldq,
                              int64_t ldk, int64_t ldv, int64_t ldo, const int32_t* cu_seqlens, int32_t B, int32_t H,
                              int32_t head_dim, int32_t max_seqlen, float softmax_scale, int32_t out_k32_rows,
-                             const int32_t* item_skip, int32_t q_prescaled, void* part_ws, size_t part_ws_bytes, void* stream) {
+                             const int32_t* item_skip, int32_t q_prescaled, void* part_ws, size_t part_ws_bytes, void* stream,
+                             int64_t total_rows) {
   if (!q || !k || !v || !out || !cu_seqlens || B <= 0 || H <= 0 || max_seqlen <= 0 || out_k32_rows < 0)
     return OMNI_ERR_BAD_ARG;
   if (head_dim != DH) return OMNI_ERR_UNSUPPORTED;
@@ -698,16 +717,16 @@ int omni_internal_flash_attn(const omni_bf16* q, const omni_bf16* k, const omni_
   if ((long)B * H * ((max_seqlen + 255) / 256) >= 512 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
       (out_k32_rows || ldo % 8 == 0))                       // its epilogue stores whole 16-byte pieces
     return omni_internal_flash_attn_w64(q, k, v, out, ldq, ldk, ldv, ldo, cu_seqlens, B, H, max_seqlen, softmax_scale,
-                                        out_k32_rows, item_skip, q_prescaled, part_ws, part_ws_bytes, stream);
+                                        out_k32_rows, item_skip, q_prescaled, part_ws, part_ws_bytes, stream, total_rows);
 #endif
 #ifdef OMNI_DEV
 #include "dev/attention_dev_dispatch.inc"
 #endif
   if (attn_pipe_waves(B * H, max_seqlen) == 8)
     return launch_pipe<8>(q, k, v, out, ldq, ldk, ldv, ldo, cu_seqlens, B, H, max_seqlen, softmax_scale, out_k32_rows, s, item_skip,
-                          q_prescaled);
+                          q_prescaled, total_rows);
   return launch_pipe<4>(q, k, v, out, ldq, ldk, ldv, ldo, cu_seqlens, B, H, max_seqlen, softmax_scale, out_k32_rows, s, item_skip,
-                        q_prescaled);
+                        q_prescaled, total_rows);
 }
 
 extern "C" int omni_flash_attn_fwd_ex(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, omni_bf16* out,

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
     uint16_t* __restrict__ out, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
     const int32_t* __restrict__ cu_seqlens, int n_heads_total, int H, float scale_log2e, int out_k32_rows,
     const int32_t* __restrict__ item_skip, int q_prescaled, int qfull, int nsplit, float* __restrict__ part_o,
-    float* __restrict__ part_ml) {
+    float* __restrict__ part_ml, int compact_B) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -257,7 +257,17 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
     sp = r - hb * nsplit;
     qb = qfull;
   }
-  const int b = hb / H, h = hb - b * H;
+  // compact grid (common.h omni_attn_compact_slots; compact_B = number of items, 0 = legacy): the list is (head, slot), the host
+  // passed n_heads_total = H and qfull = slots per head, so hb is the head and qb the slot; no split mode there
+  int b, h;
+  if (compact_B) {
+    h = hb;
+    if (!omni_attn_slot_lookup(cu_seqlens, compact_B, QBLK, qb, b, qb)) return;
+    hb = b * H + h;
+  } else {
+    b = hb / H;
+    h = hb - b * H;
+  }
   if (item_skip && item_skip[b]) return;
   const int seq_start = cu_seqlens[b];
   const int seq_len = cu_seqlens[b + 1] - seq_start;
@@ -816,7 +826,7 @@ size_t omni_internal_flash_attn_w64_ws_bytes(int32_t B, int32_t H) {
 int omni_internal_flash_attn_w64(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, omni_bf16* out, int64_t ldq,
                                  int64_t ldk, int64_t ldv, int64_t ldo, const int32_t* cu_seqlens, int32_t B, int32_t H,
                                  int32_t max_seqlen, float softmax_scale, int32_t out_k32_rows, const int32_t* item_skip,
-                                 int32_t q_prescaled, void* part_ws, size_t part_ws_bytes, void* stream) {
+                                 int32_t q_prescaled, void* part_ws, size_t part_ws_bytes, void* stream, int64_t total_rows) {
   static std::atomic<uint64_t> attr_done{0};
   OMNI_TRY_STATUS(omni_once_per_device(attr_done, [] {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_w64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -824,17 +834,26 @@ int omni_internal_flash_attn_w64(const omni_bf16* q, const omni_bf16* k, const o
   }));
   const int qblocks = (max_seqlen + QBLK - 1) / QBLK;
   const int nh = B * H;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // items of unequal length: the compact head-major slot grid where it is smaller (common.h: the rule and why).  The key-range
+  // split of the short last q-block is off in this mode: its makespan model assumes one sequence length
+  if (const int slots = omni_attn_compact_slots(total_rows, B, max_seqlen, QBLK)) {
+    hipLaunchKernelGGL(flash_attn_fwd_w64_kernel, dim3(H * slots), dim3(256), LDS_BYTES, s, q, k, v, out, ldq, ldk, ldv, ldo,
+                       cu_seqlens, H, H, softmax_scale * 1.4426950408889634f, out_k32_rows, item_skip, q_prescaled, slots, 1,
+                       nullptr, nullptr, B);
+    OMNI_CHECK_LAUNCH();
+    return OMNI_OK;
+  }
   int nsplit = 1;
   if (part_ws && (reinterpret_cast<uintptr_t>(part_ws) & 15) == 0)
     nsplit = w64_split_factor(nh, max_seqlen / QBLK, max_seqlen, omni_num_cus(), part_ws_bytes);
-  hipStream_t s = static_cast<hipStream_t>(stream);
   if (nsplit > 1) {
     const int qfull = max_seqlen / QBLK;
     float* part_o = static_cast<float*>(part_ws);
     float* part_ml = part_o + (size_t)nh * nsplit * 64 * DH;
     hipLaunchKernelGGL(flash_attn_fwd_w64_kernel, dim3(nh * qfull + nh * nsplit), dim3(256), LDS_BYTES, s, q, k, v, out, ldq, ldk,
                        ldv, ldo, cu_seqlens, nh, H, softmax_scale * 1.4426950408889634f, out_k32_rows, item_skip, q_prescaled, qfull,
-                       nsplit, part_o, part_ml);
+                       nsplit, part_o, part_ml, 0);
     OMNI_CHECK_LAUNCH();
     hipLaunchKernelGGL(attn_split_combine_kernel, dim3(nh), dim3(256), 0, s, out, ldo, out_k32_rows, cu_seqlens, H, qfull, nsplit,
                        part_o, part_ml, item_skip);
@@ -843,7 +862,7 @@ int omni_internal_flash_attn_w64(const omni_bf16* q, const omni_bf16* k, const o
   }
   hipLaunchKernelGGL(flash_attn_fwd_w64_kernel, dim3(nh * qblocks), dim3(256), LDS_BYTES, s, q, k, v, out, ldq, ldk, ldv, ldo,
                      cu_seqlens, nh, H, softmax_scale * 1.4426950408889634f, out_k32_rows, item_skip, q_prescaled, qblocks, 1,
-                     nullptr, nullptr);
+                     nullptr, nullptr, 0);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }

@@ -149,7 +149,8 @@ static inline int omni_num_cus() {
 int omni_internal_flash_attn_w64(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, omni_bf16* out, int64_t ldq,
                                  int64_t ldk, int64_t ldv, int64_t ldo, const int32_t* cu_seqlens, int32_t B, int32_t H,
                                  int32_t max_seqlen, float softmax_scale, int32_t out_k32_rows, const int32_t* item_skip,
-                                 int32_t q_prescaled, void* part_ws, size_t part_ws_bytes, void* stream);
+                                 int32_t q_prescaled, void* part_ws, size_t part_ws_bytes, void* stream,
+                                 int64_t total_rows = 0);
 size_t omni_internal_flash_attn_w64_ws_bytes(int32_t B, int32_t H);
 
 // internal (not part of the C-ABI): dst[i] = src[idx[i]] for int32 maps; used by omni_dit_forward
@@ -162,7 +163,8 @@ int omni_internal_silu_bf16(omni_bf16* dst, const omni_bf16* src, int64_t n, voi
 int omni_internal_flash_attn(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, omni_bf16* out, int64_t ldq,
                              int64_t ldk, int64_t ldv, int64_t ldo, const int32_t* cu_seqlens, int32_t B, int32_t H,
                              int32_t head_dim, int32_t max_seqlen, float softmax_scale, int32_t out_k32_rows,
-                             const int32_t* item_skip, int32_t q_prescaled, void* part_ws, size_t part_ws_bytes, void* stream);
+                             const int32_t* item_skip, int32_t q_prescaled, void* part_ws, size_t part_ws_bytes, void* stream,
+                             int64_t total_rows = 0);
 // internal: SAGE_ATTN (attention_sage.hip) — omni_flash_attn_general's qk_int8 path with a per-item device skip predicate and
 // q_prescaled = 1 for a q that already carries softmax_scale * log2(e); workspace / alignment checked here, the rest by the caller
 int omni_internal_sage_attn(const omni_attn_params* p, const int32_t* item_skip, int32_t q_prescaled, void* stream);
@@ -181,6 +183,41 @@ static inline int omni_dev_env_int(const char* name, int dflt) {
 }
 #else
 static inline int omni_dev_env_int(const char*, int dflt) { return dflt; }
+#endif
+
+// ---- Compact attention grid for items of UNEQUAL length (the three bf16 attention kernels; attention.hip, attention_w64.hip).
+// Legacy grid: B * H * ceil(max_seqlen / Q) workgroups, item-major; the workgroups of q-blocks an item does not have return at
+// once.  With very unequal items most of the grid is such workgroups, and — worse — the XCD-aware order hands every XCD a
+// CONTIGUOUS range of the item-major list, so some XCDs get the long items and the others almost nothing.
+// Compact grid: H * slots workgroups, slots = total_rows / Q + B  >=  sum_i ceil(len_i / Q)   (each ceil adds less than one),
+// HEAD-major: workgroup (h, slot) walks cu_seqlens (wave-uniform: scalar loads) to its (item, q-block); slots behind the last
+// real block return.  Every XCD's contiguous range then holds every item of a few heads.  The arithmetic of a q-block does
+// not depend on which workgroup runs it: outputs are bit-identical to the legacy grid's.
+// THE RULE, stated once: compact only where its bound is SMALLER than the legacy grid.  For equal lengths L it never is
+// (B * ceil(L / Q) <= floor(B L / Q) + B), so every equal-length launch is the launch it always was.  total_rows = 0: the caller
+// does not know the total (cu_seqlens is device memory: omni_flash_attn_fwd*) -> legacy.  Returns slots per head, 0 = legacy.
+// In compact mode the key-range split of the short last q-block (attention_w64.hip) is OFF: its makespan model assumes one length.
+constexpr int OMNI_ATTN_COMPACT_MAX_ITEMS = 64;
+static inline int omni_attn_compact_slots(int64_t total_rows, int B, int max_seqlen, int Q) {
+  static const int knob = omni_dev_env_int("OMNI_ATTN_COMPACT", 1);      // dev knob (-DOMNI_DEV builds only): 0 = always legacy
+  if (!knob || total_rows <= 0 || B > OMNI_ATTN_COMPACT_MAX_ITEMS) return 0;
+  const int64_t slots = total_rows / Q + B, legacy = (int64_t)B * ((max_seqlen + Q - 1) / Q);
+  return slots < legacy && slots < (1 << 20) ? (int)slots : 0;
+}
+#ifdef __HIPCC__
+// slot -> (item b, q-block qb) of the compact grid; false: the slot lies behind the last real block.  On success b < B and
+// qb * Q < len_b.
+__device__ static inline bool omni_attn_slot_lookup(const int32_t* __restrict__ cu_seqlens, int B, int Q, int slot, int& b, int& qb) {
+  int prev = cu_seqlens[0];
+  for (int i = 0; i < B; ++i) {
+    const int next = cu_seqlens[i + 1];
+    const int nb = (next - prev + Q - 1) / Q;
+    if (slot < nb) { b = i; qb = slot; return true; }
+    slot -= nb;
+    prev = next;
+  }
+  return false;
+}
 #endif
 
 // every AGPR, as a clobber list: makes the kernel descriptor allocate the accumulator half of the register file and tells the

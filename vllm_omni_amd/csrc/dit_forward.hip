@@ -301,7 +301,7 @@ int run_block(const omni_dit_weights* w, int l, const omni_dit_batch* b, const W
   } else
   OMNI_TRY(omni_internal_flash_attn(ws.q, ws.k, ws.v, ws.attn, D, D, D, D, b->cu_seqlens, b->n_items, w->num_heads,
                                     w->head_dim, b->max_seqlen, sm_scale, bRj, pr.item, q_prescale ? 1 : 0, ws.attn_part,
-                                    ws.attn_part_bytes, stream));
+                                    ws.attn_part_bytes, stream, b->n_joint_rows));
   }  // phase != BLOCK_POST
   const omni_bf16* attn_src = phase == BLOCK_POST ? attn_in : ws.attn;
   const int32_t attn_k32 = phase == BLOCK_POST ? 0 : bRj;       // a caller-provided attention output is row-major

@@ -7,7 +7,8 @@ therefore per-request B=1 semantics; this module lets several requests (and the 
 request) share a DiT forward WITHOUT padding: rows of all items are concatenated, and small int32 maps tell the
 kernels which item / joint row / RoPE position every token belongs to.
 
-Item i contributes T_i text rows and S_img image rows.  Three row spaces:
+Item i contributes T_i text rows and S_i image rows (S_i = the tokens of item i's latent grid; the items of a forward
+may sit on DIFFERENT grids, see `build_ragged_batch`).  Three row spaces:
   image stream  [n_img_rows]  item-major                 (residual stream `hidden_states`)
   text stream   [n_txt_rows]  item-major                 (residual stream `encoder_hidden_states`)
   joint         [n_joint_rows] per item [text_i ; image_i]  (q/k/v/attention; reference order, :412-416)
@@ -23,11 +24,11 @@ import torch
 @dataclass
 class RaggedBatch:
     txt_lens: list[int]
-    s_img: int
+    s_imgs: list[int]             # image rows of every item
     temb_rows: list[int]          # item -> row of the timestep-embedding table (items may share one)
     n_temb: int
-    grid: tuple                   # (frames, h/16, w/16) latent token grid, or a tuple of such triples (target + condition
-                                  # images on one sequence axis), identical for all items
+    grids: tuple                  # per item: (frames, h/16, w/16) latent token grid, or a tuple of such triples (target +
+                                  # condition images on one sequence axis)
     txt_pos_end: int              # rope table rows [0, txt_pos_end) are text positions
     img_start: int = 0            # first image token of the grid held by this batch (sequence-parallel chunk)
     cu_seqlens: np.ndarray = field(repr=False, default=None)
@@ -42,8 +43,45 @@ class RaggedBatch:
         return len(self.txt_lens)
 
     @property
+    def mixed(self) -> bool:
+        """Do the items sit on more than one grid?"""
+        return any(g != self.grids[0] for g in self.grids)
+
+    @property
+    def distinct_grids(self) -> tuple:
+        """The grids of this batch in order of first appearance (the segment order of the RoPE table)."""
+        return tuple(dict.fromkeys(self.grids))
+
+    @property
+    def n_txt_pos(self) -> int:
+        """Text positions per distinct grid: the RoPE table holds one text segment of this length for each of them."""
+        return self.txt_pos_end // len(self.distinct_grids)
+
+    @property
+    def s_img(self) -> int:
+        """Image rows per item of a batch on ONE grid; a mixed batch has no such number (use `s_imgs`)."""
+        if self.mixed:
+            raise ValueError("items of this batch sit on different grids: there is no common s_img, use s_imgs")
+        return self.s_imgs[0]
+
+    @property
+    def grid(self) -> tuple:
+        """The grid of a batch on ONE grid; a mixed batch has no such grid (use `grids`)."""
+        if self.mixed:
+            raise ValueError("items of this batch sit on different grids: there is no common grid, use grids")
+        return self.grids[0]
+
+    @property
     def n_img_rows(self) -> int:
-        return self.n_items * self.s_img
+        return int(sum(self.s_imgs))
+
+    @property
+    def img_offsets(self) -> list[int]:
+        """First image-stream row of every item, and the total behind the last."""
+        offs = [0]
+        for s in self.s_imgs:
+            offs.append(offs[-1] + s)
+        return offs
 
     @property
     def n_txt_rows(self) -> int:
@@ -55,49 +93,113 @@ class RaggedBatch:
 
     @property
     def max_seqlen(self) -> int:
-        return max(self.txt_lens) + self.s_img
+        return max(t + s for t, s in zip(self.txt_lens, self.s_imgs))
 
     def device_maps(self, device) -> dict[str, torch.Tensor]:
         names = ("cu_seqlens", "img_item", "txt_item", "img_joint_row", "txt_joint_row", "joint_pos")
         return {n: torch.from_numpy(getattr(self, n)).to(device) for n in names}
 
 
-def build_ragged_batch(txt_lens: list[int], grid: tuple[int, int, int], temb_rows: list[int] | None = None,
+def _per_item_grids(grid, n: int):
+    """`grid` as a tuple of n normalised per-item grids.  A LIST with one entry per item is the per-item form; anything else
+    (a triple, a tuple of triples: the Edit pipelines' multi-entry grid) is one grid that every item sits on."""
+    from .models.qwen_image.rope import normalize_grids
+
+    def one(g):
+        g = normalize_grids(g)
+        return g[0] if len(g) == 1 else g               # one image: the plain (f, h, w) triple; several: a tuple of triples
+
+    if isinstance(grid, list) and grid and all(isinstance(g, (list, tuple)) for g in grid):
+        if len(grid) != n:
+            raise ValueError(f"{len(grid)} per-item grids for {n} items")
+        return tuple(tuple(one(tuple(g))) for g in grid)
+    return (tuple(one(grid)),) * n
+
+
+def build_ragged_batch(txt_lens: list[int], grid, temb_rows: list[int] | None = None,
                        txt_pos_end: int | None = None, img_rows: tuple[int, int] | None = None) -> RaggedBatch:
-    """Build the int32 row maps for items with text lengths `txt_lens` on a common latent grid.
+    """Build the int32 row maps for items with text lengths `txt_lens`.  `grid`: one latent grid common to all items, or a
+    LIST of grids, one per item (requests of different resolutions in one forward).
     `img_rows = (start, count)`: every item holds only that slice of the grid's image tokens (a sequence-parallel rank's
-    chunk, reference qwen_image_transformer.py:735-738,772-781); RoPE positions stay those of the full grid."""
+    chunk, reference qwen_image_transformer.py:735-738,772-781); RoPE positions stay those of the full grid.  One grid only.
+
+    RoPE positions (`joint_pos`, rows of models/qwen_image/rope.py `rope_table_multi`): the table of a forward is laid out
+    [text segment of distinct grid 0 | text segment of grid 1 | ... | image segment of grid 0 | image segment of grid 1 | ...],
+    every text segment `n_txt` rows long (n_txt = the `txt_pos_end` argument, default the longest prompt), because the text
+    positions of an item start behind ITS grid's half-extent.  The batch's `txt_pos_end` is the end of the last text segment,
+    so "rows below txt_pos_end are text positions" holds for any number of grids; with one grid the layout is the
+    single-grid table's."""
     if not txt_lens or any(t <= 0 for t in txt_lens):
         raise ValueError("every item needs at least one text token")
-    from .models.qwen_image.rope import grid_tokens, normalize_grids
+    from .models.qwen_image.rope import grid_tokens
 
-    grid = normalize_grids(grid)
-    grid = grid[0] if len(grid) == 1 else grid          # one image: the plain (f, h, w) triple; several: a tuple of triples
-    total = grid_tokens(grid)
-    img_start, s_img = (0, total) if img_rows is None else (int(img_rows[0]), int(img_rows[1]))
-    if img_start < 0 or s_img <= 0 or img_start + s_img > total:
-        raise ValueError("img_rows outside the token grid")
     n = len(txt_lens)
+    grids = _per_item_grids(grid, n)
+    distinct = tuple(dict.fromkeys(grids))
+    totals = [grid_tokens(g) for g in grids]
+    if img_rows is None:
+        img_start, s_imgs = 0, totals
+    else:
+        if len(distinct) != 1:
+            raise ValueError("img_rows (a sequence-parallel chunk) needs one grid for all items")
+        img_start, s_imgs = int(img_rows[0]), [int(img_rows[1])] * n
+        if img_start < 0 or s_imgs[0] <= 0 or img_start + s_imgs[0] > totals[0]:
+            raise ValueError("img_rows outside the token grid")
     temb_rows = list(range(n)) if temb_rows is None else list(temb_rows)
     if len(temb_rows) != n:
         raise ValueError("temb_rows must have one entry per item")
     tmax = max(txt_lens)
-    txt_pos_end = tmax if txt_pos_end is None else txt_pos_end
-    if txt_pos_end < tmax:
+    n_txt = tmax if txt_pos_end is None else txt_pos_end
+    if n_txt < tmax:
         raise ValueError("txt_pos_end smaller than the longest prompt")
-    seq = np.asarray([t + s_img for t in txt_lens], dtype=np.int64)
+    # table row of the first text / image position of every distinct grid
+    seg = {g: k for k, g in enumerate(distinct)}
+    txt_pos_end = n_txt * len(distinct)
+    img_seg0, o = {}, txt_pos_end
+    for g in distinct:
+        img_seg0[g] = o
+        o += grid_tokens(g)
+    seq = np.asarray([t + s for t, s in zip(txt_lens, s_imgs)], dtype=np.int64)
     cu = np.zeros(n + 1, dtype=np.int32)
     cu[1:] = np.cumsum(seq)
-    img_item = np.repeat(np.asarray(temb_rows, dtype=np.int32), s_img)
+    img_item = np.repeat(np.asarray(temb_rows, dtype=np.int32), s_imgs)
     txt_item = np.repeat(np.asarray(temb_rows, dtype=np.int32), txt_lens)
-    img_joint = np.concatenate([cu[i] + txt_lens[i] + np.arange(s_img, dtype=np.int32) for i in range(n)])
+    img_joint = np.concatenate([cu[i] + txt_lens[i] + np.arange(s_imgs[i], dtype=np.int32) for i in range(n)])
     txt_joint = np.concatenate([cu[i] + np.arange(txt_lens[i], dtype=np.int32) for i in range(n)])
     joint_pos = np.empty(int(cu[-1]), dtype=np.int32)
     for i in range(n):
-        joint_pos[cu[i]: cu[i] + txt_lens[i]] = np.arange(txt_lens[i], dtype=np.int32)
-        joint_pos[cu[i] + txt_lens[i]: cu[i + 1]] = txt_pos_end + img_start + np.arange(s_img, dtype=np.int32)
-    return RaggedBatch(txt_lens=list(txt_lens), s_img=s_img, temb_rows=temb_rows, n_temb=max(temb_rows) + 1,
-                       grid=tuple(grid), txt_pos_end=txt_pos_end, img_start=img_start, cu_seqlens=cu,
+        joint_pos[cu[i]: cu[i] + txt_lens[i]] = seg[grids[i]] * n_txt + np.arange(txt_lens[i], dtype=np.int32)
+        joint_pos[cu[i] + txt_lens[i]: cu[i + 1]] = img_seg0[grids[i]] + img_start + np.arange(s_imgs[i], dtype=np.int32)
+    return RaggedBatch(txt_lens=list(txt_lens), s_imgs=list(s_imgs), temb_rows=temb_rows, n_temb=max(temb_rows) + 1,
+                       grids=grids, txt_pos_end=txt_pos_end, img_start=img_start, cu_seqlens=cu,
                        img_item=img_item.astype(np.int32), txt_item=txt_item.astype(np.int32),
                        img_joint_row=img_joint.astype(np.int32), txt_joint_row=txt_joint.astype(np.int32),
                        joint_pos=joint_pos)
+
+
+# ---- the compact attention grid for items of unequal length: host model of csrc/common.h (omni_attn_compact_slots,
+# omni_attn_slot_lookup).  The kernels do this on the device; these functions state the same rule for tests and tools.
+ATTN_COMPACT_MAX_ITEMS = 64
+
+
+def attention_compact_slots(seq_lens: list[int], qblk: int) -> int:
+    """Slots per head of the compact grid, or 0 when the launch keeps the legacy grid of len(seq_lens) * ceil(max / qblk)
+    workgroups per head.  The bound sum // qblk + B needs only integers the host has (n_joint_rows, n_items, max_seqlen); it
+    covers sum_i ceil(len_i / qblk) because every ceil adds less than one, and for equal lengths it is never below the legacy
+    grid, so such launches never change."""
+    B = len(seq_lens)
+    if B > ATTN_COMPACT_MAX_ITEMS or sum(seq_lens) <= 0:
+        return 0
+    slots = sum(seq_lens) // qblk + B
+    legacy = B * -(-max(seq_lens) // qblk)
+    return slots if slots < legacy else 0
+
+
+def attention_slot_lookup(cu_seqlens, qblk: int, slot: int):
+    """slot -> (item, q-block) by the walk over cu_seqlens the kernels do; None for a slot behind the last real block."""
+    for i in range(len(cu_seqlens) - 1):
+        nb = -(-(int(cu_seqlens[i + 1]) - int(cu_seqlens[i])) // qblk)
+        if slot < nb:
+            return i, slot
+        slot -= nb
+    return None

@@ -106,6 +106,11 @@ class OmniDiffusionConfig:
                                      # a request's prompt / latents / seed (QwenImageTransformer2DModel.modulation_table_for_schedule)
     max_steps_in_flight: int = 2     # NEW: how many denoising steps a worker's host may enqueue ahead of the device
                                      # (step_batcher.py: bounded run-ahead, so that a newcomer joins within this many steps)
+    mixed_step_batch: bool = False   # NEW, opt-in: text-to-image requests of DIFFERENT resolutions and true-CFG scales share a
+                                     # DiT forward (the batch key drops the grid and the scale).  Off: every batch
+                                     # key and every code path is what it was
+    max_step_tokens: int | None = None  # NEW: admission bound next to max_step_batch — the largest sum of image rows x CFG
+                                     # branches one forward may hold (the oldest sample always runs, alone if need be)
     # ---- the reference's remaining fields (data.py:255-360), so that a config written for it constructs here unchanged.
     # Inert here (nothing on this path depends on them, results are the same either way): executor / server plumbing, HF hub
     # options, CPU-offload and pinning switches (41 GB of weights stay resident in 288 GB of HBM), VAE slicing, torch.compile

@@ -543,10 +543,19 @@ class QwenImagePipeline(nn.Module):
 
     SERVE_MAX_STEPS = 1024
 
-    @staticmethod
-    def batch_key(a):
+    def batch_key(self, a):
+        """What one ragged forward can mix.  Default: one token grid and one true-CFG scale per forward.  With
+        `od_config.mixed_step_batch` plain text-to-image samples of ANY grid and scale share a key (the kernels address rows
+        through per-item maps; the CFG + Euler update runs per request).  The grid stays in the key for samples that carry
+        condition rows (Edit / Edit-Plus / Layered: multi-entry grids) and whenever TeaCache is configured (its reductions
+        assume equal image rows per item)."""
         sm = a.sample
+        if getattr(self.od_config, "mixed_step_batch", False) and sm.get("cond") is None and not self._teacache_configured():
+            return ("mixed", sm["do_cfg"], sm.get("cfg_normalize", True), sm.get("t_cond"))
         return (sm["grid"], sm["do_cfg"], sm["cfg"], sm.get("cfg_normalize", True), sm.get("t_cond"))
+
+    def _teacache_configured(self) -> bool:
+        return self.cache_backend is not None or getattr(self.transformer, "teacache", None) is not None
 
     # A "serve state" = everything one composition of a running batch needs, allocated ONCE: the static input / output
     # buffers of the forward, the ragged-batch descriptor, the per-request timestep / dt vectors, the TeaCache device state
@@ -563,23 +572,46 @@ class QwenImagePipeline(nn.Module):
         lens = [int(a.state["pos"].shape[0]) for a in group] + ([int(a.state["neg"].shape[0]) for a in group] if do_cfg else [])
         tcfg = getattr(tr, "teacache", None)
         use_tab = bool(getattr(self.od_config, "precompute_modulation", True))
-        key = (tuple(lens), tuple(sm0["grid"]), do_cfg, float(sm0["cfg"]), R, S_c, sm0.get("cfg_normalize", True), sm0.get("t_cond"),
-               use_tab, None if tcfg is None else (tcfg.rel_l1_thresh, tuple(tcfg.coefficients)))
+        # a MIXED group: requests on different token grids and / or with different true-CFG scales in one forward
+        grids = [tuple(a.sample["grid"]) for a in group]
+        cfgs = [float(a.sample["cfg"]) for a in group]
+        mixed = len(set(grids)) > 1 or len(set(cfgs)) > 1
+        if mixed:
+            if any(a.sample["do_cfg"] != do_cfg for a in group):
+                raise NotImplementedError("a mixed step-batch cannot combine requests with and without true-CFG")
+            if any(a.state.get("cond") is not None for a in group):
+                raise NotImplementedError("a mixed step-batch cannot hold samples with condition-image rows (Edit / Edit-Plus / "
+                                          "Layered): their multi-entry grids must be the same for every item of a forward")
+            if tcfg is not None:
+                raise NotImplementedError("a mixed step-batch cannot run with TeaCache: its residual reductions assume the same "
+                                          "number of image rows for every item (omni_teacache)")
+        S_list = [int(a.state["lat"].shape[0]) for a in group]
+        img_off = [0]
+        for s_ in S_list:
+            img_off.append(img_off[-1] + s_)                  # slot r's latent rows: [img_off[r], img_off[r + 1]); r * S when equal
+        if mixed:      # the key names the ordered sizes and scales (the batcher orders a group longest first: canonical)
+            key = ("mixed", tuple(lens), tuple(grids), do_cfg, tuple(cfgs), R, sm0.get("cfg_normalize", True), sm0.get("t_cond"), use_tab)
+        else:
+            key = (tuple(lens), tuple(sm0["grid"]), do_cfg, float(sm0["cfg"]), R, S_c, sm0.get("cfg_normalize", True), sm0.get("t_cond"),
+                   use_tab, None if tcfg is None else (tcfg.rel_l1_thresh, tuple(tcfg.coefficients)))
         st = self._serve_states.get(key)
         if st is not None:
             return st
         n_items, S_tot, Cl = (2 if do_cfg else 1) * R, S + S_c, tr.in_channels
-        rb = build_ragged_batch(lens, sm0["grid"], temb_rows=list(range(R)) * (2 if do_cfg else 1))
+        n_lat = img_off[-1]                                   # latent rows of all slots (R * S when equal)
+        rb = build_ragged_batch(lens, (grids * (2 if do_cfg else 1)) if mixed else sm0["grid"],
+                                temb_rows=list(range(R)) * (2 if do_cfg else 1))
         offs = [0]
         for t in lens:
             offs.append(offs[-1] + t)
         st = dict(key=key, R=R, S=S, S_c=S_c, do_cfg=do_cfg, cfg=float(sm0["cfg"]), n_items=n_items, rb=rb, txt_off=offs,
+                  mixed=mixed, cfgs=cfgs, img_off=img_off, n_lat=n_lat,
                   cfg_normalize=bool(sm0.get("cfg_normalize", True)), t_cond=sm0.get("t_cond"),
                   temb_add=None if sm0.get("t_cond") is None else tr.time_text_embed.additional_rows([sm0["t_cond"]] * R, R),
                   prepared=tr.prepare_batch(rb), members=[None] * R, graph=None, gen=None,
-                  lat=torch.zeros(R * S, Cl, dtype=BF16, device=dev),
-                  lat_in=torch.zeros(n_items * S_tot, Cl, dtype=BF16, device=dev),
-                  pred=torch.empty(n_items * S_tot, Cl, dtype=BF16, device=dev),
+                  lat=torch.zeros(n_lat, Cl, dtype=BF16, device=dev),
+                  lat_in=torch.zeros(rb.n_img_rows, Cl, dtype=BF16, device=dev),
+                  pred=torch.empty(rb.n_img_rows, Cl, dtype=BF16, device=dev),
                   pred_c=torch.empty(n_items * S, Cl, dtype=BF16, device=dev) if S_c else None,
                   prompt=torch.zeros(sum(lens), tr.joint_attention_dim, dtype=BF16, device=dev),
                   sig=torch.zeros(R, dtype=torch.float32, device=dev), dt=torch.zeros(R, dtype=torch.float32, device=dev),
@@ -608,8 +640,8 @@ class QwenImagePipeline(nn.Module):
         if home is None:
             return
         st, r = home
-        S, R = st["S"], st["R"]
-        a.state["lat"] = st["lat"][r * S:(r + 1) * S].clone()
+        R, off = st["R"], st["img_off"]
+        a.state["lat"] = st["lat"][off[r]:off[r + 1]].clone()
         if st["tc"] is not None:
             a.state["tc"] = [st["tc"].export_item(r)] + ([st["tc"].export_item(R + r)] if st["do_cfg"] else [])
         st["members"][r] = None
@@ -624,7 +656,7 @@ class QwenImagePipeline(nn.Module):
         if occ is not None and occ is not a:
             self._export_sample(occ)
         S, S_c, R, do_cfg = st["S"], st["S_c"], st["R"], st["do_cfg"]
-        st["lat"][r * S:(r + 1) * S].copy_(a.state["lat"])
+        st["lat"][st["img_off"][r]:st["img_off"][r + 1]].copy_(a.state["lat"])
         n = a.state["sig_d"].shape[0]
         st["sig_tab"][r, :n].copy_(a.state["sig_d"])
         st["dt_tab"][r, :n].copy_(a.state["dt_d"])
@@ -650,7 +682,7 @@ class QwenImagePipeline(nn.Module):
         tr = self.transformer
         R, S, S_c, do_cfg, n_items = st["R"], st["S"], st["S_c"], st["do_cfg"], st["n_items"]
         lat, lat_in, pred = st["lat"], st["lat_in"], st["pred"]
-        Cl = lat.shape[1]
+        Cl, n_lat = lat.shape[1], st["n_lat"]
         idx = st["step_idx"].clamp(max=self.SERVE_MAX_STEPS - 1).view(R, 1)
         st["sig"].copy_(st["sig_tab"].gather(1, idx).view(R))
         st["dt"].copy_(st["dt_tab"].gather(1, idx).view(R))
@@ -660,17 +692,26 @@ class QwenImagePipeline(nn.Module):
             if do_cfg:
                 li[R:, :S].copy_(lat.view(R, S, Cl))
         else:
-            lat_in[: R * S].copy_(lat)
+            lat_in[: n_lat].copy_(lat)
             if do_cfg:
-                lat_in[R * S:].copy_(lat)
+                lat_in[n_lat:].copy_(lat)
         tr.forward_ragged(st["prepared"], lat_in, st["prompt"], st["sig"], out=pred, teacache=st["tc"], temb_add=st["temb_add"],
                           mod_table=st["mod"])
         pr = pred
         if S_c:                                              # noise_pred[:, :latents.size(1)] (edit pipeline :632)
             st["pred_c"].view(n_items, S, Cl).copy_(pred.view(n_items, S + S_c, Cl)[:, :S])
             pr = st["pred_c"]
-        ops.cfg_euler_step_(lat, pr[: R * S], pr[R * S:] if do_cfg else None, st["cfg"], st["dt"], dt_rows_per_item=S,
-                            normalize=st["cfg_normalize"])
+        if st["mixed"]:
+            # one launch of the fused CFG + Euler kernel per request, on that request's row slice: its own scale, its own dt
+            # (dt_rows_per_item = 0: the kernel reads dt[0] of the pointer it is given)
+            off = st["img_off"]
+            for r in range(R):
+                o0, o1 = off[r], off[r + 1]
+                ops.cfg_euler_step_(lat[o0:o1], pr[o0:o1], pr[n_lat + o0:n_lat + o1] if do_cfg else None, st["cfgs"][r],
+                                    st["dt"][r:r + 1], dt_rows_per_item=0, normalize=st["cfg_normalize"])
+        else:
+            ops.cfg_euler_step_(lat, pr[: R * S], pr[R * S:] if do_cfg else None, st["cfg"], st["dt"], dt_rows_per_item=S,
+                                normalize=st["cfg_normalize"])
         st["step_idx"].add_(1)
 
     @torch.no_grad()
@@ -696,7 +737,7 @@ class QwenImagePipeline(nn.Module):
                 st["mod"][:, :, r].copy_(a.state["mod_tab"][:, :, min(a.step, a.n_steps - 1)])
         tr.do_true_cfg = st["do_cfg"]
         self.last_teacache_state = st["tc"]
-        if not self._use_graph(st["n_items"] * st["S"]):
+        if not self._use_graph((2 if st["do_cfg"] else 1) * st["n_lat"]):
             self._serve_step_body(st)
             return
         tr._native_weights()

@@ -26,7 +26,7 @@ from ...batch import RaggedBatch, build_ragged_batch
 from ...layers.adalayernorm import AdaLayerNorm
 from .... import _native as N
 from .... import ops
-from .rope import grid_tokens, normalize_grids, rope_table
+from .rope import grid_tokens, normalize_grids, rope_table, rope_table_multi
 
 BF16 = torch.bfloat16
 
@@ -537,12 +537,15 @@ class QwenImageTransformer2DModel(nn.Module):
     # ------------------------------------------------------------------ batches
     def prepare_batch(self, batch: RaggedBatch) -> dict:
         """Upload the int32 maps and the bf16 RoPE table of a RaggedBatch (cache by content)."""
-        key = (tuple(batch.txt_lens), tuple(batch.temb_rows), batch.grid, batch.txt_pos_end, batch.img_start, batch.s_img)
+        if batch.mixed:      # the per-item description; a batch on one grid keeps the key it always had
+            key = (tuple(batch.txt_lens), tuple(batch.temb_rows), batch.grids, batch.txt_pos_end, batch.img_start, tuple(batch.s_imgs))
+        else:
+            key = (tuple(batch.txt_lens), tuple(batch.temb_rows), batch.grid, batch.txt_pos_end, batch.img_start, batch.s_img)
         hit = self._batch_cache.get(key)
         if hit is not None:
             return hit
         dev = self.device
-        cos, sin = rope_table(batch.grid, batch.txt_pos_end)
+        cos, sin = rope_table_multi(batch.distinct_grids, batch.n_txt_pos)
         ent = dict(batch=batch, maps=batch.device_maps(dev), cos=cos.to(dev, BF16).contiguous(),
                    sin=sin.to(dev, BF16).contiguous())
         if len(self._batch_cache) > 32:

@@ -81,3 +81,23 @@ def _rope_table(grids: tuple[tuple[int, ...], ...], n_txt_pos: int) -> tuple[tor
 def rope_table(grid, n_txt_pos: int) -> tuple[torch.Tensor, torch.Tensor]:
     """(cos, sin) fp32 CPU tensors of shape [n_txt_pos + n_image_tokens, 64]; rows [0, n_txt_pos) are text positions."""
     return _rope_table(normalize_grids(grid), int(n_txt_pos))
+
+
+def rope_table_multi(grids, n_txt_pos: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """ONE table for a forward whose items sit on several grids (`grids`: the DISTINCT grids, in the order
+    diffusion/batch.py `RaggedBatch.distinct_grids` lists them):
+
+        [text segment of grid 0 | text segment of grid 1 | ... | image segment of grid 0 | image segment of grid 1 | ...]
+
+    Every text segment has `n_txt_pos` rows — the text positions start at max(h // 2, w // 2) of the item's OWN grid, so two
+    grids cannot share them — and all of them lie in front of every image row: rows [0, len(grids) * n_txt_pos) are text
+    positions, which is what the q/k norm kernel's `txt_pos_end` test relies on.  Each segment is a slice of the
+    single-grid table of its grid, bit for bit; with one grid the result IS that table."""
+    grids = tuple(grids)
+    if len(grids) == 1:
+        return rope_table(grids[0], n_txt_pos)
+    n = int(n_txt_pos)
+    tabs = [rope_table(g, n) for g in grids]
+    cos = torch.cat([c[:n] for c, _ in tabs] + [c[n:] for c, _ in tabs], dim=0)
+    sin = torch.cat([s[:n] for _, s in tabs] + [s[n:] for _, s in tabs], dim=0)
+    return cos, sin

@@ -35,6 +35,10 @@ class ContinuousStepBatcher:
         cfg = getattr(pipeline, "od_config", None)
         cap = max_items or int(getattr(cfg, "max_step_batch", 4) or 4)
         self.max_samples = max(1, cap)
+        # second, optional bound (mixed-resolution groups: a count of samples says little about the size of a forward): the
+        # largest sum of image rows x CFG branches a forward may hold.  None: the count alone decides, as it always did
+        tok = getattr(cfg, "max_step_tokens", None)
+        self.max_tokens = None if tok is None else max(1, int(tok))
         self.active: list[ActiveSample] = []
         self._pending: dict[Any, dict] = {}        # tag -> {"req": request, "left": samples still running, "done": {k: lat}}
         self._seq = itertools.count()
@@ -116,7 +120,13 @@ class ContinuousStepBatcher:
         ROUND-ROBIN — the key whose last forward lies furthest back goes next, so traffic at one resolution never waits behind
         another resolution's whole loop; within a key admission is FIFO: the `max_samples` oldest samples run, a waiting sample
         takes the first slot that frees up (continuous batching with a bounded batch, not time slicing — time slicing would
-        re-compose the batch every step for no gain in throughput)."""
+        re-compose the batch every step for no gain in throughput).
+
+        With `max_step_tokens` set, the oldest samples of the key are taken while BOTH bounds hold; the oldest one is always
+        admitted, so a request larger than the budget still runs (alone).  A key that can mix sizes (the pipeline's
+        `mixed_step_batch`) hands its group over LONGEST ITEM FIRST, stable by arrival: within every head's range of the
+        attention grid the long items' blocks are issued first, and the pipeline's per-composition state is keyed by the ordered sizes, so one
+        multiset of sizes maps to one state."""
         by_key: dict[Any, list[ActiveSample]] = {}
         for a in sorted(self.active, key=lambda a: a.seq):
             by_key.setdefault(self.pipeline.batch_key(a), []).append(a)
@@ -125,7 +135,32 @@ class ContinuousStepBatcher:
         key = min(by_key, key=lambda k: (self._last_served.get(k, -1), by_key[k][0].seq))
         self._tick += 1
         self._last_served[key] = self._tick
-        return by_key[key][: self.max_samples]
+        if self.max_tokens is None:
+            group = by_key[key][: self.max_samples]
+        else:
+            group, used = [], 0
+            for a in by_key[key][: self.max_samples]:
+                t = self._tokens(a)
+                if group and used + t > self.max_tokens:
+                    break
+                group.append(a)
+                used += t
+        if all(a.sample.get("lat") is not None for a in group) and len({self._rows(a) for a in group}) > 1:
+            group = sorted(group, key=lambda a: (-self._rows(a), a.seq))
+        return group
+
+    @staticmethod
+    def _rows(a: ActiveSample) -> int:
+        """Image rows of the sample (`sample["lat"]`: [rows, channels]).  Only consulted when a group can differ in size or a token
+        budget is set; a pipeline that uses either must put the latents into its samples."""
+        lat = a.sample.get("lat")
+        if lat is None:
+            raise ValueError("max_step_tokens / mixed step batches need the sample's latents (sample['lat']) to size it")
+        return int(lat.shape[0])
+
+    def _tokens(self, a: ActiveSample) -> int:
+        """Image rows x CFG branches: what the sample adds to a forward."""
+        return self._rows(a) * (2 if a.sample.get("do_cfg") else 1)
 
     def step(self) -> list[tuple[Any, Any]]:
         """Advance one group of active samples by one denoising step; return finished (tag, output)s."""
