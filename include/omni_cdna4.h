@@ -47,6 +47,11 @@ typedef enum {
 int omni_abi_version(void);
 const char* omni_build_arch(void);
 const char* omni_status_string(int status);
+/* Optional capabilities, as a bit set.  A field that moves into former struct padding (omni_attn_params.elem_type) keeps the
+ * ABI version, so the version cannot tell a library that reads it from one that does not: a caller that is about to set such
+ * a field asks here first (and treats a library without this symbol as having no optional capability). */
+#define OMNI_FEATURE_ATTN_F16 1u /* omni_flash_attn_general reads omni_attn_params.elem_type and has fp16 kernels */
+uint32_t omni_features(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Grouped GEMM with fused epilogue:  Y_g = epilogue(A_g · W_gᵀ + bias_g)  for g < ngroups (<= 2).
@@ -346,7 +351,16 @@ int omni_flash_attn_fwd_ws(const omni_bf16* q, const omni_bf16* k, const omni_bf
  *   mask_type 1: one byte per element, non-zero = attend (torch.bool); 2: bf16 added to the scaled scores; 3: fp32 added.
  *   causal = 1: key j takes part in query i only if j <= i (torch's is_causal: aligned to the top-left corner).
  *   out = softmax(scale * q k^T + mask) v per (item, head), fp32 softmax; rows with no key to attend to produce zeros.
- * head_dim 64 or 128 (OMNI_ERR_UNSUPPORTED otherwise); H % H_kv == 0. */
+ * head_dim 64 or 128 (OMNI_ERR_UNSUPPORTED otherwise); H % H_kv == 0.
+ *   elem_type (needs OMNI_FEATURE_ATTN_F16): OMNI_ELEM_BF16 (0) — q, k, v and out are bf16, as in every other entry point;
+ *   OMNI_ELEM_F16 (1) — q, k, v and out are ALL IEEE fp16 bit patterns: both products run on the fp16 MFMA, P and the output
+ *   are rounded to fp16 (nearest even), the softmax stays fp32.  The mask does not follow: mask_type 2 still means bf16 (hand
+ *   an fp16 additive mask over as fp32).  qk_int8 = 1 with fp16 is OMNI_ERR_UNSUPPORTED; any other elem_type value is
+ *   OMNI_ERR_BAD_ARG.  The field occupies what used to be padding behind mask_type — size and every other offset are
+ *   unchanged — so callers MUST zero the whole struct (memset / `= {0}` / `= {}`) before filling it in; a caller that never
+ *   heard of the field then asks for bf16. */
+#define OMNI_ELEM_BF16 0
+#define OMNI_ELEM_F16 1
 typedef struct {
   const omni_bf16 *q, *k, *v;
   omni_bf16* out;
@@ -359,6 +373,7 @@ typedef struct {
   int32_t causal;
   const void* mask;
   int32_t mask_type;                   /* 0 none, 1 bool bytes, 2 bf16 additive, 3 fp32 additive */
+  int32_t elem_type;                   /* OMNI_ELEM_BF16 / OMNI_ELEM_F16: type of q, k, v, out (sits in former padding) */
   int64_t mask_stride_b, mask_stride_h, mask_stride_q, mask_stride_k;
   /* ABI v14 — appended; all zero = the bf16 kernel above, bit for bit.
    * qk_int8 = 1: SAGE_ATTN (the reference's sage_attn.py backend, SageAttention v1: int8 Q K^T, fp32 softmax, bf16 P V), per item

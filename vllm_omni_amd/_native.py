@@ -76,7 +76,7 @@ class AttnParams(C.Structure):
         ("B", C.c_int32), ("H", C.c_int32), ("H_kv", C.c_int32), ("head_dim", C.c_int32),
         ("max_seqlen_q", C.c_int32), ("max_seqlen_k", C.c_int32),
         ("softmax_scale", C.c_float), ("causal", C.c_int32),
-        ("mask", C.c_void_p), ("mask_type", C.c_int32),
+        ("mask", C.c_void_p), ("mask_type", C.c_int32), ("elem_type", C.c_int32),      # elem_type: former padding
         ("mask_stride_b", C.c_int64), ("mask_stride_h", C.c_int64), ("mask_stride_q", C.c_int64), ("mask_stride_k", C.c_int64),
         ("qk_int8", C.c_int32), ("out_k32_rows", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),  # ABI v14
         ("item_skip", c_i32_p),
@@ -161,6 +161,7 @@ PROTOTYPES = {
     "omni_abi_version": (C.c_int, []),
     "omni_build_arch": (C.c_char_p, []),
     "omni_status_string": (C.c_char_p, [C.c_int]),
+    "omni_features": (C.c_uint32, []),            # capability bits; OPTIONAL (see lib()): a library of the same ABI version may lack it
     "omni_gemm_bf16": (C.c_int, [C.POINTER(GemmParams), C.c_void_p]),
     "omni_quantize_fp8_rows": (C.c_int, [c_bf16_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_void_p]),
@@ -221,6 +222,12 @@ PROTOTYPES = {
                                       c_bf16_p, C.c_void_p]),
 }
 
+# symbols a library of the SAME ABI version may lack: they were added together with a field that went into former struct
+# padding, which keeps the version.  `features()` is how callers ask.
+OPTIONAL_SYMBOLS = ("omni_features",)
+FEATURE_ATTN_F16 = 1                              # OMNI_FEATURE_ATTN_F16
+ELEM_BF16, ELEM_F16 = 0, 1                        # omni_attn_params.elem_type
+
 _lib = None
 _lock = threading.Lock()
 
@@ -242,6 +249,8 @@ def lib() -> C.CDLL:
             try:
                 fn = getattr(dll, name)
             except AttributeError as e:  # pragma: no cover
+                if name in OPTIONAL_SYMBOLS:
+                    continue
                 raise OmniNativeError(f"{LIB_PATH} does not export {name}") from e
             fn.restype = res
             fn.argtypes = args
@@ -256,3 +265,9 @@ def check(status: int, what: str) -> None:
     if status != 0:
         msg = lib().omni_status_string(status).decode()
         raise OmniNativeError(f"{what} failed: status {status} ({msg})")
+
+
+def features() -> int:
+    """omni_features(): the capability bits of the loaded library; 0 for a library that does not export the symbol."""
+    fn = getattr(lib(), "omni_features", None)
+    return int(fn()) if fn is not None else 0

@@ -6,15 +6,17 @@
 //   * attention masks: boolean (True = attend) or additive (bf16 / fp32), any layout broadcastable to [B, H, S_q, S_k]
 //     (element strides, 0 = broadcast) — key-padding masks, block masks, dense biases,
 //   * is_causal (top-left aligned like torch: key index <= query index),
-//   * grouped K / V heads (num_kv_heads < num_heads).
+//   * grouped K / V heads (num_kv_heads < num_heads),
+//   * q / k / v / out in fp16 as well as bf16 (omni_attn_params.elem_type; the reference runs its DiTs in either, data.py:418-436):
+//     the kernel is a template on the element type, the bf16 instances are what they were.
 // Same arithmetic scheme as attention.hip, with hipcc scheduling the loop (no hand-placed waits: this is the general path, not
 // the roofline kernel):
 //   one workgroup = 4 waves x 32 queries of one (item, head); K / V tiles of 64 keys staged global -> registers -> LDS, the
 //   next tile's global loads in flight while the current tile is consumed;
-//   S^T = K Q^T with SWAPPED operands (v_mfma_f32_32x32x16_bf16: A = K fragment, B = Q fragment kept in registers), so a lane
+//   S^T = K Q^T with SWAPPED operands (v_mfma_f32_32x32x16_bf16 / _f16: A = K fragment, B = Q fragment kept in registers), so a lane
 //   owns ONE query and 16 of a 32-key sub-block's scores: scale, mask, running max / sum are lane-local, the two half-waves
 //   exchange one value per tile (v_permlane32_swap);
-//   O^T += V^T P^T: B = P^T is the exp'ed S^T accumulator packed to bf16 (its C-layout key order is adopted as the MFMA k
+//   O^T += V^T P^T: B = P^T is the exp'ed S^T accumulator packed to bf16 / fp16 (its C-layout key order is adopted as the MFMA k
 //   order), A = V^T fragments by ds_read_b64_tr_b16 from a row-major V tile in the blocked image [d/32][key/4][4 keys][32 d].
 //   fp32 softmax in the exp2 domain; scores are scaled in fp32 (q is NOT pre-rounded with the scale).
 // Rows whose every key is masked produce zeros (torch's math path yields NaN there, its fused paths zeros).
@@ -30,12 +32,30 @@ constexpr int GKV = 64;                // keys per tile
 typedef __attribute__((ext_vector_type(4))) short g_s16x4_t;
 typedef __attribute__((address_space(3))) g_s16x4_t g_lds_s16x4;
 
-OMNI_DEVINL bf16x8_t g_tr_read_pair(uint32_t a, uint32_t b) {
+// The element type of q / k / v / out (omni_attn_params.elem_type): the 8-element MFMA fragment, the 32x32x16 MFMA and the
+// round-to-nearest-even pack of two fp32 values.  Everything else of the kernel (addresses, softmax, masks) is type-blind.
+template <bool F16>
+struct g_elem;
+template <>
+struct g_elem<false> {
+  typedef bf16x8_t frag;
+  static OMNI_DEVINL f32x16_t mfma(frag a, frag b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+  static OMNI_DEVINL uint32_t pack2(float lo, float hi) { return pack_bf16x2(lo, hi); }
+};
+template <>
+struct g_elem<true> {
+  typedef f16x8_t frag;
+  static OMNI_DEVINL f32x16_t mfma(frag a, frag b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+  static OMNI_DEVINL uint32_t pack2(float lo, float hi) { return pack_f16x2(lo, hi); }
+};
+
+template <typename FRAG>
+OMNI_DEVINL FRAG g_tr_read_pair(uint32_t a, uint32_t b) {
   g_s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((g_lds_s16x4*)(uintptr_t)a);
   g_s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((g_lds_s16x4*)(uintptr_t)b);
   typedef __attribute__((ext_vector_type(8))) short s16x8_t;
   s16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8_t, v);
+  return __builtin_bit_cast(FRAG, v);
 }
 OMNI_DEVINL float g_xhalf_max(float x) {
   uint32_t a = __builtin_bit_cast(uint32_t, x), b = a;
@@ -48,8 +68,14 @@ OMNI_DEVINL float g_xhalf_sum(float x) {
   return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
 }
 
-template <int DH>
+// F16: q / k / v / out are IEEE fp16 and both products run on v_mfma_f32_32x32x16_f16; P and the output are rounded to fp16
+// (nearest even).  P = exp2(s - m) <= 1 goes to the MFMA as it is, also where it is an fp16 SUBNORMAL (below 6.1e-5): measured,
+// the fp16 MFMA does not flush subnormal operands (a tail of 4095 keys 10 - 13 nats below the maximum keeps its 5.5 % of the
+// mass: DESIGN.md kernel table, tests/test_gpu_attention_fp16.py flat tail), so no exponent shift of P is needed.
+template <int DH, bool F16>
 __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const omni_attn_params P, int qblocks) {
+  typedef g_elem<F16> E;
+  typedef typename E::frag frag_t;
   constexpr int NCH = DH / 8;              // 16-byte chunks per K / V row
   constexpr int ROWB = DH * 2;             // bytes per K row in LDS
   constexpr int NKS = DH / 16;             // MFMA k-steps of the QK^T product
@@ -73,11 +99,11 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
   const int qrow = min(qi, q_len - 1);
 
   // Q fragments: B operand of S^T = K Q^T — lane (query l31, half hi) holds k = 16 ks + 8 hi .. + 8
-  bf16x8_t qf[NKS];
+  frag_t qf[NKS];
   {
     const uint16_t* qp = P.q + (int64_t)(q_start + qrow) * P.ldq + h * DH + hi * 8;
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + ks * 16);
+    for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const frag_t*>(qp + ks * 16);
   }
   f32x16_t o[NDB];
 #pragma unroll
@@ -134,7 +160,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
   for (int t = 0; t < ntiles; ++t) {
     if (t + 1 < ntiles) load_tile(t + 1);                    // in flight while tile t is consumed
     // ---- S^T = K Q^T: two 32-key sub-blocks
-    typedef __attribute__((address_space(3))) const bf16x8_t lds_bf16x8;
+    typedef __attribute__((address_space(3))) const frag_t lds_frag;
     f32x16_t s[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -142,8 +168,8 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
       for (int i = 0; i < 16; ++i) s[j][i] = 0.0f;
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
-        const bf16x8_t kf = *reinterpret_cast<lds_bf16x8*>((uintptr_t)(k_addr[ks] + j * 32 * ROWB));
-        s[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s[j], 0, 0, 0);
+        const frag_t kf = *reinterpret_cast<lds_frag*>((uintptr_t)(k_addr[ks] + j * 32 * ROWB));
+        s[j] = E::mfma(kf, qf[ks], s[j]);
       }
     }
     // ---- scale, mask, online softmax.  register r of sub-block j <-> key t*64 + 32 j + (r & 3) + 8 (r >> 2) + 4 hi
@@ -224,7 +250,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
       for (int r = 0; r < 16; r += 2) {
         const float p0 = __builtin_amdgcn_exp2f(s[j][r] - m_use), p1 = __builtin_amdgcn_exp2f(s[j][r + 1] - m_use);
         psum += p0 + p1;
-        pk[j][r >> 3][(r >> 1) & 3] = pack_bf16x2(p0, p1);
+        pk[j][r >> 3][(r >> 1) & 3] = E::pack2(p0, p1);
       }
     l_run = l_run * alpha + psum;
 #pragma unroll
@@ -237,12 +263,12 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
         const u32x4_t p4 = {pk[j][hf][0], pk[j][hf][1], pk[j][hf][2], pk[j][hf][3]};
-        const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, p4);
+        const frag_t pf = __builtin_bit_cast(frag_t, p4);
 #pragma unroll
         for (int d = 0; d < NDB; ++d) {
           const uint32_t va = v_addr + d * 4096 + (j * 8 + hf * 4) * 256;
-          const bf16x8_t vf = g_tr_read_pair(va, va + 512);
-          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[d], 0, 0, 0);
+          const frag_t vf = g_tr_read_pair<frag_t>(va, va + 512);
+          o[d] = E::mfma(vf, pf, o[d]);
         }
       }
     __syncthreads();                                         // every wave is done with tile t
@@ -262,19 +288,19 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
 #pragma unroll
       for (int qd = 0; qd < 4; ++qd) {
         u32x2_t w;
-        w[0] = pack_bf16x2(o[d][qd * 4 + 0] * inv, o[d][qd * 4 + 1] * inv);
-        w[1] = pack_bf16x2(o[d][qd * 4 + 2] * inv, o[d][qd * 4 + 3] * inv);
+        w[0] = E::pack2(o[d][qd * 4 + 0] * inv, o[d][qd * 4 + 1] * inv);
+        w[1] = E::pack2(o[d][qd * 4 + 2] * inv, o[d][qd * 4 + 3] * inv);
         *reinterpret_cast<u32x2_t*>(op + d * 32 + qd * 8) = w;
       }
   }
 }
 
-template <int DH>
+template <int DH, bool F16>
 int launch_general(const omni_attn_params* p, hipStream_t s) {
   const int qblocks = (p->max_seqlen_q + GQBLK - 1) / GQBLK;
   const long grid = (long)p->B * p->H * qblocks;
   if (grid <= 0 || grid > 0x7fffffffL) return OMNI_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((flash_attn_general_kernel<DH>), dim3((unsigned)grid), dim3(GQ_WAVES * 64), 0, s, *p, qblocks);
+  hipLaunchKernelGGL((flash_attn_general_kernel<DH, F16>), dim3((unsigned)grid), dim3(GQ_WAVES * 64), 0, s, *p, qblocks);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }
@@ -290,7 +316,9 @@ extern "C" int omni_flash_attn_general(const omni_attn_params* p, omni_stream st
   if (p->head_dim != 64 && p->head_dim != 128) return OMNI_ERR_UNSUPPORTED;
   if (p->qk_int8 != 0 && p->qk_int8 != 1) return OMNI_ERR_BAD_ARG;
   if (p->out_k32_rows < 0) return OMNI_ERR_BAD_ARG;
+  if (p->elem_type != OMNI_ELEM_BF16 && p->elem_type != OMNI_ELEM_F16) return OMNI_ERR_BAD_ARG;
   if (p->qk_int8 == 1 && (p->mask_type != 0 || p->causal)) return OMNI_ERR_UNSUPPORTED;
+  if (p->qk_int8 == 1 && p->elem_type != OMNI_ELEM_BF16) return OMNI_ERR_UNSUPPORTED;           // SAGE_ATTN is bf16 only
   if (p->qk_int8 == 0 && (p->out_k32_rows != 0 || p->item_skip)) return OMNI_ERR_UNSUPPORTED;   // the int8 path's options
   if (!omni_aligned16(p->q) || !omni_aligned16(p->k) || !omni_aligned16(p->v) || (reinterpret_cast<uintptr_t>(p->out) & 7) ||
       (p->ldq % 8) || (p->ldk % 8) || (p->ldv % 8) || (p->ldo % 4))
@@ -299,5 +327,10 @@ extern "C" int omni_flash_attn_general(const omni_attn_params* p, omni_stream st
   if (p->mask_type == 3 && (reinterpret_cast<uintptr_t>(p->mask) & 3)) return OMNI_ERR_ALIGN;
   if (p->qk_int8 == 1) return omni_internal_sage_attn(p, p->item_skip, 0, stream);     // SAGE_ATTN: attention_sage.hip
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return p->head_dim == 128 ? launch_general<128>(p, s) : launch_general<64>(p, s);
+  if (p->elem_type == OMNI_ELEM_F16) return p->head_dim == 128 ? launch_general<128, true>(p, s) : launch_general<64, true>(p, s);
+  return p->head_dim == 128 ? launch_general<128, false>(p, s) : launch_general<64, false>(p, s);
 }
+
+// Optional capabilities of this build that the ABI version does not tell (fields that went into former struct padding keep
+// the version, so a caller has to be able to ask whether the library reads them).
+extern "C" uint32_t omni_features(void) { return OMNI_FEATURE_ATTN_F16; }

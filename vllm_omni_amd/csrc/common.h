@@ -31,6 +31,22 @@ OMNI_DEVINL uint32_t pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
+// fp16 twins of the bf16 helpers above (omni_attn_params.elem_type = OMNI_ELEM_F16).  The plain _Float16 cast rounds to nearest
+// even (v_cvt_f16_f32 / v_cvt_pk_f16_f32 under the default rounding mode) — NOT __builtin_amdgcn_cvt_pkrtz, which truncates.
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;   // one MFMA A/B fragment (4 VGPRs)
+typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+OMNI_DEVINL float f16_bits_to_f32(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
+OMNI_DEVINL float f16_lo(uint32_t w) { return (float)__builtin_bit_cast(f16x2_t, w)[0]; }
+OMNI_DEVINL float f16_hi(uint32_t w) { return (float)__builtin_bit_cast(f16x2_t, w)[1]; }
+OMNI_DEVINL uint16_t f32_to_f16_bits(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
+OMNI_DEVINL uint32_t pack_f16x2(float lo, float hi) {
+  f16x2_t v;
+  v[0] = (_Float16)lo;
+  v[1] = (_Float16)hi;
+  return __builtin_bit_cast(uint32_t, v);
+}
+
 OMNI_DEVINL float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 // GELU tanh approximation: 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)))  == x * sigmoid(2u)
 // = x / (1 + exp(-2u)), u = sqrt(2/pi) (x + 0.044715 x^3), as 7 VALU operations: the exponent is formed directly in the

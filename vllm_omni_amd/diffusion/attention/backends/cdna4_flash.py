@@ -12,6 +12,12 @@ and cached (attention/selector.py:49-77), so whatever is registered also serves 
 
 q/k/v arrive as [B, S, H, dh] ("NHD"); the kernels consume exactly that layout (flattened over B, S with uniform
 cu_seqlens), so unlike SDPAImpl there is no permute (sdpa.py:53,65).
+
+dtypes: q, k and v share one of torch.bfloat16 / torch.float16 (the reference runs its DiTs in either, diffusion/data.py:418-436)
+and the output has it; anything else is a ValueError here, before the library is touched.  fp16 ALWAYS runs on
+`omni_flash_attn_general` — also the no-mask, head-size-128, S_q == S_kv case bf16 sends to the tuned kernels, which are
+bf16-only.  fp16 self-attention is therefore served by the general (hipcc-scheduled) kernel, not by a roofline kernel
+(kernel table).
 """
 import torch
 
@@ -19,6 +25,7 @@ from .... import ops
 from .abstract import AttentionBackend, AttentionImpl, AttentionMetadata
 
 HEAD_SIZES = (64, 128)
+DTYPES = (torch.bfloat16, torch.float16)
 
 
 def _mask_strides(mask: torch.Tensor, B: int, H: int, Sq: int, Sk: int) -> tuple[torch.Tensor, tuple[int, int, int, int]]:
@@ -57,6 +64,9 @@ class CDNA4FlashImpl(AttentionImpl):
 
     def forward(self, query, key, value, attn_metadata: AttentionMetadata = None) -> torch.Tensor:
         mask = attn_metadata.attn_mask if attn_metadata is not None else None
+        if query.dtype not in DTYPES or key.dtype != query.dtype or value.dtype != query.dtype:
+            raise ValueError(f"CDNA4_FLASH takes q, k, v of ONE dtype out of torch.bfloat16 / torch.float16, got q {query.dtype}, "
+                             f"k {key.dtype}, v {value.dtype} (cast them; the backend does not convert silently)")
         B, Sq, H, dh = query.shape
         Sk, Hkv = key.shape[1], key.shape[2]
         if H != self.num_heads or dh != self.head_size or Hkv != self.num_kv_heads or value.shape != key.shape or key.shape[0] != B:
@@ -65,7 +75,7 @@ class CDNA4FlashImpl(AttentionImpl):
         q2 = query.reshape(B * Sq, H * dh)
         k2, v2 = key.reshape(B * Sk, Hkv * dh), value.reshape(B * Sk, Hkv * dh)
         cu_q = self._cu_seqlens(B, Sq, query.device)
-        if mask is None and not self.causal and Sq == Sk and dh == 128 and Hkv == H:
+        if query.dtype == torch.bfloat16 and mask is None and not self.causal and Sq == Sk and dh == 128 and Hkv == H:
             out = ops.flash_attn_varlen(q2, k2, v2, cu_q, H, Sq, self.softmax_scale)          # the tuned self-attention kernels
         else:
             m, strides = (None, None) if mask is None else _mask_strides(mask.to(query.device), B, H, Sq, Sk)

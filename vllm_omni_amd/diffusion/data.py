@@ -3,12 +3,35 @@
 Field names and defaults follow the reference so configs written for it construct here unchanged."""
 from __future__ import annotations
 
+import logging
 from collections.abc import Callable
 from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import Any
 
 import torch
+
+logger = logging.getLogger(__name__)
+
+# string spellings of `OmniDiffusionConfig.dtype` (reference data.py:418-436)
+_DTYPE_STRINGS = {
+    "auto": torch.bfloat16, "bfloat16": torch.bfloat16, "bf16": torch.bfloat16,
+    "float16": torch.float16, "fp16": torch.float16, "half": torch.float16,
+    "float32": torch.float32, "fp32": torch.float32, "float": torch.float32,
+}
+
+
+def require_fused_bf16(od_config, who: str) -> None:
+    """The fused Qwen-Image path (DiT GEMMs, tuned attention, elementwise and VAE kernels) exists in bf16 only.  A config that
+    asks for another dtype is refused where that path is BUILT — construction of the config itself stays permissive, because a
+    plug-in user (another DiT on the CDNA4_FLASH attention backend, which does take fp16) passes the same config legitimately."""
+    dtype = getattr(od_config, "dtype", torch.bfloat16)
+    if dtype != torch.bfloat16:
+        raise NotImplementedError(
+            f"{who}: od_config.dtype is {dtype}, but the fused DiT / VAE kernels of this path are bf16 (storage bf16, fp32 "
+            "accumulate).  fp16 is served at the attention plug-in point (the CDNA4_FLASH backend takes fp16 q / k / v), not by "
+            "the fused Qwen-Image pipeline; running bf16 instead would not be what was asked, so this is refused rather than "
+            "ignored.  Use dtype=torch.bfloat16 here.")
 
 
 _PARALLEL_AXES = ("pipeline_parallel_size", "data_parallel_size", "tensor_parallel_size", "ulysses_degree",
@@ -80,7 +103,9 @@ class TransformerConfig(dict):
 class OmniDiffusionConfig:
     model: str | None = None
     model_class_name: str | None = "QwenImagePipeline"
-    dtype: torch.dtype = torch.bfloat16
+    dtype: torch.dtype = torch.bfloat16   # or one of the reference's strings ("fp16", "half", ...).  HONOURED OR REFUSED, never
+                                     # ignored: the fused Qwen-Image path is bf16 and refuses anything else where it is built
+                                     # (`require_fused_bf16`); fp16 runs at the attention plug-in point (CDNA4_FLASH backend)
     tf_model_config: TransformerConfig = field(default_factory=TransformerConfig)
     parallel_config: DiffusionParallelConfig = field(default_factory=DiffusionParallelConfig)
     cache_backend: str = "none"
@@ -169,6 +194,12 @@ class OmniDiffusionConfig:
             self.tf_model_config = TransformerConfig.from_dict(self.tf_model_config)
         if self.num_gpus is None:
             self.num_gpus = self.parallel_config.world_size
+        if isinstance(self.dtype, str):          # the reference's table and its fallback (data.py:418-436)
+            known = _DTYPE_STRINGS.get(self.dtype.lower())
+            if known is None:
+                logger.warning("Unknown dtype string '%s', defaulting to bfloat16", self.dtype)
+                known = torch.bfloat16
+            self.dtype = known
         if self.cache_backend is None:
             self.cache_backend = "none"
         if self.cache_backend not in ("none", "tea_cache", "teacache"):

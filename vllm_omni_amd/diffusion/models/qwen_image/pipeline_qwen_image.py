@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from .... import ops
 from ...batch import build_ragged_batch
-from ...data import DiffusionOutput, OmniDiffusionConfig
+from ...data import DiffusionOutput, OmniDiffusionConfig, require_fused_bf16
 from ...request import OmniDiffusionRequest
 from .autoencoder_kl_qwenimage import AutoencoderKLQwenImage
 from .qwen_image_transformer import QwenImageTransformer2DModel
@@ -54,6 +54,7 @@ class QwenImagePipeline(nn.Module):
                  transformer_kwargs: dict | None = None, text_encoder=None):
         super().__init__()
         self.od_config = od_config or OmniDiffusionConfig()
+        require_fused_bf16(self.od_config, type(self).__name__)
         dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
         self.device = dev
         self.transformer = transformer if transformer is not None else QwenImageTransformer2DModel(

@@ -16,7 +16,7 @@ import traceback
 
 import torch
 
-from ..data import DiffusionOutput, OmniDiffusionConfig
+from ..data import DiffusionOutput, OmniDiffusionConfig, require_fused_bf16
 from ..distributed import data_parallel as dp
 from ..request import OmniDiffusionRequest
 
@@ -24,6 +24,7 @@ from ..request import OmniDiffusionRequest
 class GPUWorker:
     def __init__(self, local_rank: int, rank: int, od_config: OmniDiffusionConfig, pipeline=None):
         self.local_rank, self.rank, self.od_config = local_rank, rank, od_config
+        require_fused_bf16(od_config, "GPUWorker")
         self.pipeline = pipeline
         self.world = 1
         self.sp_degree, self.sp_group, self.dp_rank, self.dp_world = 1, None, rank, 1

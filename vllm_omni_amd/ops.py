@@ -312,6 +312,7 @@ def flash_attn_workspace_floats(B: int, H: int) -> int:
 
 
 _MASK_TYPES = {torch.bool: 1, torch.uint8: 1, torch.bfloat16: 2, torch.float32: 3}
+ATTN_ELEM_TYPES = {torch.bfloat16: N.ELEM_BF16, torch.float16: N.ELEM_F16}      # omni_attn_params.elem_type
 
 
 def flash_attn_general(q, k, v, cu_seqlens_q, cu_seqlens_k, num_heads: int, num_kv_heads: int, max_seqlen_q: int,
@@ -325,11 +326,22 @@ def flash_attn_general(q, k, v, cu_seqlens_q, cu_seqlens_k, num_heads: int, num_
     `qk_int8` (ABI v14): SAGE_ATTN — int8 Q K^T with smoothed K (include/omni_cdna4.h omni_attn_params.qk_int8); no mask, not
     causal.  Its device workspace is `workspace` (uint8, at least attn_quant_workspace_bytes(...) bytes) or allocated here.
     `out_k32_blocked` (int8 path only): out holds the K32-blocked order [H*dh/32][rows][32].  `item_skip` (int8 path only):
-    int32 DEVICE [B]; items with a non-zero entry are not computed and their output rows are left as they are."""
+    int32 DEVICE [B]; items with a non-zero entry are not computed and their output rows are left as they are.
+    q, k, v (and `out`) share ONE dtype, bf16 or fp16 (omni_attn_params.elem_type); the output has it too.  fp16 needs a
+    library that reports OMNI_FEATURE_ATTN_F16 and has no qk_int8 path.  A bf16 mask stays bf16 whatever q is."""
+    dts = [t.dtype for t in (q, k, v) + (() if out is None else (out,))]
+    if q.dtype not in ATTN_ELEM_TYPES or any(d != q.dtype for d in dts):
+        raise N.OmniNativeError("q, k, v and out must share one dtype out of torch.bfloat16 / torch.float16, got "
+                                + ", ".join(str(d) for d in dts))
+    et = q.dtype
+    if et == torch.float16 and not N.features() & N.FEATURE_ATTN_F16:
+        raise N.OmniNativeError("this libomni_cdna4.so does not report OMNI_FEATURE_ATTN_F16: it would read fp16 q / k / v as "
+                                "bf16 bits — rebuild it (python vllm_omni_amd/csrc/build.py)")
     rows, HD, ldq = _rows2d(q, "q")
-    o = torch.empty(rows, HD, dtype=BF16, device=q.device) if out is None else out
+    o = torch.empty(rows, HD, dtype=et, device=q.device) if out is None else out
     p = N.AttnParams()
-    p.q, p.k, p.v, p.out = _p(q, name="q"), _p(k, name="k"), _p(v, name="v"), _p(o, name="out")
+    p.q, p.k, p.v, p.out = _p(q, et, name="q"), _p(k, et, name="k"), _p(v, et, name="v"), _p(o, et, name="out")
+    p.elem_type = ATTN_ELEM_TYPES[et]
     p.ldq, p.ldk, p.ldv, p.ldo = ldq, k.stride(0), v.stride(0), o.stride(0)
     p.cu_seqlens_q, p.cu_seqlens_k = _p(cu_seqlens_q, torch.int32, "cu_seqlens_q"), _p(cu_seqlens_k, torch.int32, "cu_seqlens_k")
     p.B, p.H, p.H_kv, p.head_dim = cu_seqlens_q.numel() - 1, num_heads, num_kv_heads, HD // num_heads
