@@ -261,32 +261,23 @@ def test_fp16_instances_use_the_fp16_mfma_and_round_to_nearest_even():
         assert "_f16" not in text, name
 
 
-def test_bf16_instances_are_instruction_for_instruction_what_they_were(tmp_path):
-    """The parent commit's attention_general.hip and common.h (the file the fp16 helpers went into), compiled with today's
-    header — the struct the kernel receives by value has the same size and offsets."""
+def test_bf16_instances_are_instruction_for_instruction_what_they_were():
+    """Templating the kernel on the element type cost the bf16 instances nothing: a bf16 instance and the fp16 instance of
+    the same head size are the SAME instruction stream — same registers, same order — except for the two things the element
+    policy (attention_common.h attn_elem) names: the 32x32x16 MFMA and the nearest-even pack.  (When the template was
+    introduced this was checked against the untemplated kernel of the commit before; that comparison needs that commit and
+    cannot outlive a change of the kernel, this one holds for every later form of it.)"""
     from vllm_omni_amd.csrc import build as B
 
-    def show(path, rev):
-        r = subprocess.run(["git", "-C", ROOT, "show", f"{rev}:{path}"], capture_output=True, text=True)
-        return r.stdout if r.returncode == 0 else None
+    bodies = _kernel_bodies(B.device_asm(os.path.join(CSRC, "attention_general.hip")))
 
-    # HEAD~ once this change is committed; HEAD while it is still the working tree
-    for rev in ("HEAD", "HEAD~"):
-        old_kernel, old_common = show("vllm_omni_amd/csrc/attention_general.hip", rev), show("vllm_omni_amd/csrc/common.h", rev)
-        if old_kernel and old_common and "template <int DH>\n__global__" in old_kernel:
-            break
-    else:
-        pytest.skip("the commit before the kernel was templated on the element type is not reachable as HEAD~")
-    d = tmp_path / "vllm_omni_amd" / "csrc"
-    d.mkdir(parents=True)
-    (tmp_path / "include").mkdir()
-    (tmp_path / "include" / "omni_cdna4.h").write_text(show("include/omni_cdna4.h", rev))
-    (d / "common.h").write_text(old_common)
-    (d / "attention_general.hip").write_text(old_kernel)
-    old = _kernel_bodies(B.device_asm(str(d / "attention_general.hip")))
-    new = _kernel_bodies(B.device_asm(os.path.join(CSRC, "attention_general.hip")))
+    def as_bf16(lines):
+        return [ln.replace("v_mfma_f32_32x32x16_f16", "v_mfma_f32_32x32x16_bf16").replace("v_cvt_pk_f16_f32", "v_cvt_pk_bf16_f32")
+                for ln in lines]
+
     for dh in (64, 128):
-        a = [v for k, v in old.items() if f"Li{dh}E" in k]
-        b = [v for k, v in new.items() if f"Li{dh}ELb0E" in k]
+        a = [v for k, v in bodies.items() if f"Li{dh}ELb0E" in k]
+        b = [v for k, v in bodies.items() if f"Li{dh}ELb1E" in k]
         assert len(a) == 1 and len(b) == 1
-        assert a[0] == b[0], f"bf16 dh {dh}: the instruction stream changed"
+        assert any("v_cvt_pk_f16_f32" in ln for ln in b[0]) and any("v_mfma_f32_32x32x16_f16" in ln for ln in b[0])
+        assert a[0] == as_bf16(b[0]), f"dh {dh}: the bf16 and fp16 instances differ in more than the MFMA and the pack"

@@ -24,7 +24,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "attention_common.h"
 
 namespace {
 
@@ -35,30 +35,11 @@ constexpr int K_TILE_BYTES = KVBLK * DH * 2;  // 16 KiB
 constexpr int STAGE_BYTES = 2 * K_TILE_BYTES; // K + V
 constexpr int LDS_BYTES = 2 * STAGE_BYTES;    // 64 KiB
 
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
-
 template <int OFF>
 OMNI_DEVINL bf16x8_t lds_read16(uint32_t addr) {   // invisible to hipcc's waitcnt pass: waits are counted by hand
   bf16x8_t v;
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
   return v;
-}
-
-template <int OFF>
-OMNI_DEVINL u32x2_t lds_tr_read8(uint32_t addr) {   // ds_read_b64_tr_b16: hardware 4x4 transpose read
-  u32x2_t v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-
-OMNI_DEVINL bf16x8_t tr_read_pair(uint32_t lds_addr_a, uint32_t lds_addr_b) {
-  // two hardware-transposed 4x(16 lanes) reads -> the 8 k-elements of one MFMA A fragment
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)lds_addr_a);
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)lds_addr_b);
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-  s16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8_t, v);
 }
 
 #ifdef OMNI_DEV
@@ -85,19 +66,6 @@ OMNI_DEVINL bf16x8_t tr_read_pair(uint32_t lds_addr_a, uint32_t lds_addr_b) {
 OMNI_DEVINL void attn_glds16(const char* tile_base, uint32_t lane_byte_off, uint32_t lds_byte_addr) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                :: "s"(lds_byte_addr), "v"(lane_byte_off), "s"(tile_base) : "memory");
-}
-// max over the two half-waves WITHOUT touching LDS (a ds_bpermute would break the counted lgkmcnt waits of the
-// fragment pipeline): v_permlane32_swap exchanges a[32..63] with b[0..31].  Inline asm with two distinct registers —
-// the builtin called with the same value for both operands is folded to one register by hipcc.
-OMNI_DEVINL float xhalf_max(float x) {
-  uint32_t a = __builtin_bit_cast(uint32_t, x), b = a;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-  return fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
-}
-OMNI_DEVINL float xhalf_sum(float x) {
-  uint32_t a = __builtin_bit_cast(uint32_t, x), b = a;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-  return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
 }
 
 #ifndef OMNI_ATTN_DMA_BURST
@@ -154,16 +122,12 @@ __global__ __launch_bounds__(NW * 64, ((NW == 4 && NQ == 1) ? 2 : 1)) void flash
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
 
-  // Block -> (item*head, q-block).  block_order 1 (default): XCD-aware.  Block b runs on XCD b % 8; each XCD gets a
-  // CONTIGUOUS range of the (head-major, q-block-minor) work list, so the ~32 workgroups resident on an XCD are all the
-  // q-blocks of about two heads: they stream the same 2 MB of K/V through that XCD's 4 MiB L2 at the same pace (one miss +
-  // 16 hits per line).  block_order 0 (round 1): heads fastest — an XCD then holds 18 different heads at once (38 MB of
-  // K/V against 4 MiB of L2: TCC hit 49 %, 5.4x the algorithmic fabric traffic, profiles/r01).
+  // Block -> (item*head, q-block).  block_order 1 (default): XCD-aware (common.h omni_xcd_contiguous) over the (head-major,
+  // q-block-minor) work list.  block_order 0 (round 1): heads fastest.
   int hb, qb;
   if (block_order == 1) {
-    const int nwg = gridDim.x, bid = blockIdx.x, qblocks = nwg / n_heads_total;
-    const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int nwg = gridDim.x, qblocks = nwg / n_heads_total;
+    const int lid = omni_xcd_contiguous(blockIdx.x, nwg);
     hb = lid / qblocks;
     qb = lid - hb * qblocks;
   } else {
@@ -224,7 +188,7 @@ __global__ __launch_bounds__(NW * 64, ((NW == 4 && NQ == 1) ? 2 : 1)) void flash
   // Only the 8 per-lane byte offsets stay live across the loop; the ragged-tail variant recomputes key / column.
   // piece P = wave + NW*i of each operand image (16 pieces of 1 KiB); V piece P = (dblk = P>>2, key group = P&3)
   auto k_key_of = [&](int i) { return 4 * (wave + NW * i) + (lane >> 4); };
-  auto k_col_of = [&](int i) { return (uint32_t)(((lane & 15) ^ (k_key_of(i) & 15)) * 16); };
+  auto k_col_of = [&](int i) { return attn_k_chunk<2 * DH>(k_key_of(i), lane & 15) * 16; };
   auto v_key_of = [&](int i) { return 16 * ((wave + NW * i) & 3) + 4 * (lane >> 4) + ((lane >> 2) & 3); };
   auto v_col_of = [&](int i) { return (uint32_t)((4 * ((wave + NW * i) >> 2) + (lane & 3)) * 16); };
   uint32_t k_src[NPIECE], v_src[NPIECE];
@@ -264,10 +228,10 @@ __global__ __launch_bounds__(NW * 64, ((NW == 4 && NQ == 1) ? 2 : 1)) void flash
 
   uint32_t k_addr[8];
 #pragma unroll
-  for (int ks = 0; ks < 8; ++ks) k_addr[ks] = lds0 + l31 * 256 + ((((uint32_t)(ks * 2 + hi)) ^ (l31 & 15)) << 4);
+  for (int ks = 0; ks < 8; ++ks) k_addr[ks] = attn_k_frag_addr<2 * DH>(lds0, lane, ks);
   // absolute LDS addresses; the stage (a compile-time constant per call site: the loop is unrolled by two) and the fragment
   // index go into the 16-bit offset immediate of the ds_reads, so the loop has no address arithmetic at all
-  const uint32_t v_addr = lds0 + K_TILE_BYTES + ((lane & 15) >> 2) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8 + hi * 256;
+  const uint32_t v_addr = attn_vt_lane_addr(lds0 + K_TILE_BYTES, lane);
 
   f32x16_t o[NQ][4];
   float m_run[NQ], l_run[NQ];
@@ -322,8 +286,7 @@ __global__ __launch_bounds__(NW * 64, ((NW == 4 && NQ == 1) ? 2 : 1)) void flash
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = kv0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        if (key >= seq_len) {
+        if (attn_key_of(kv0, j, r, hi) >= seq_len) {
 #pragma unroll
           for (int bq = 0; bq < NQ; ++bq) S[bq][j][r] = -INFINITY;
         }
@@ -495,15 +458,15 @@ __global__ __launch_bounds__(NW * 64, ((NW == 4 && NQ == 1) ? 2 : 1)) void flash
     {
       const uint32_t vb = v_addr;                 // V(t) lives in stage t & 1 = PAR: folded into the offset immediates
       u32x2_t vlo[4], vhi[4];
-#define OMNI_VOFF(i) (PAR * STAGE_BYTES + ((i) & 3) * 4096 + ((((i) >> 3) * 8 + (((i) >> 2) & 1) * 4) * 256))
+#define OMNI_VOFF(i) (PAR * STAGE_BYTES + attn_pv_off((i) & 3, (i) >> 3, ((i) >> 2) & 1))
 #define OMNI_VREAD(i)                                                                      \
   do {                                                                                     \
     if (OMNI_ATTN_ABL & 16) {                                                              \
       asm volatile("" : "=v"(vlo[(i) & 3]) : "v"(vb));                                     \
       asm volatile("" : "=v"(vhi[(i) & 3]) : "v"(vb));                                     \
     } else {                                                                               \
-      vlo[(i) & 3] = lds_tr_read8<OMNI_VOFF(i)>(vb);                                       \
-      vhi[(i) & 3] = lds_tr_read8<OMNI_VOFF(i) + 512>(vb);                                 \
+      vlo[(i) & 3] = tr_read8<OMNI_VOFF(i)>(vb);                                       \
+      vhi[(i) & 3] = tr_read8<OMNI_VOFF(i) + 512>(vb);                                 \
     }                                                                                      \
   } while (0)
 #define OMNI_PV(i)                                                                                             \
@@ -673,19 +636,14 @@ int launch_pipe(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, omni
     return hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_pipe_kernel<NW, NQ, PP>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
   }));
-  const int qblocks = (max_seqlen + 32 * NW * NQ - 1) / (32 * NW * NQ);
-  const int nh = B * H;
-  // items of unequal length: the compact head-major slot grid where it is smaller (common.h: the rule and why)
-  if (const int slots = omni_attn_compact_slots(total_rows, B, max_seqlen, 32 * NW * NQ)) {
-    hipLaunchKernelGGL((flash_attn_fwd_pipe_kernel<NW, NQ, PP>), dim3(H * slots), dim3(NW * 64), LDS_BYTES, s, q, k, v, out, ldq,
-                       ldk, ldv, ldo, cu_seqlens, H, H, softmax_scale * 1.4426950408889634f, out_k32_rows, attn_block_order(),
-                       item_skip, q_prescaled, B);
-    OMNI_CHECK_LAUNCH();
-    return OMNI_OK;
-  }
-  hipLaunchKernelGGL((flash_attn_fwd_pipe_kernel<NW, NQ, PP>), dim3(nh * qblocks), dim3(NW * 64), LDS_BYTES, s, q, k, v, out, ldq,
-                     ldk, ldv, ldo, cu_seqlens, nh, H, softmax_scale * 1.4426950408889634f, out_k32_rows, attn_block_order(), item_skip,
-                     q_prescaled, 0);
+  constexpr int QBLK = 32 * NW * NQ;
+  // items of unequal length: the compact head-major slot grid where it is smaller (common.h: the rule and why); else the
+  // legacy (item * head, q-block) grid
+  const int slots = omni_attn_compact_slots(total_rows, B, max_seqlen, QBLK);
+  const int n_heads_total = slots ? H : B * H, qblocks = slots ? slots : (max_seqlen + QBLK - 1) / QBLK;
+  hipLaunchKernelGGL((flash_attn_fwd_pipe_kernel<NW, NQ, PP>), dim3(n_heads_total * qblocks), dim3(NW * 64), LDS_BYTES, s, q, k, v,
+                     out, ldq, ldk, ldv, ldo, cu_seqlens, n_heads_total, H, softmax_scale * OMNI_LOG2E, out_k32_rows,
+                     attn_block_order(), item_skip, q_prescaled, slots ? B : 0);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }

@@ -9,64 +9,23 @@
 //   * grouped K / V heads (num_kv_heads < num_heads),
 //   * q / k / v / out in fp16 as well as bf16 (omni_attn_params.elem_type; the reference runs its DiTs in either, data.py:418-436):
 //     the kernel is a template on the element type, the bf16 instances are what they were.
-// Same arithmetic scheme as attention.hip, with hipcc scheduling the loop (no hand-placed waits: this is the general path, not
+// The arithmetic scheme of attention.hip (swapped operands: a lane owns ONE query; K / V images, V^T by transposed reads, the
+// half-wave exchange: attention_common.h), with hipcc scheduling the loop (no hand-placed waits: this is the general path, not
 // the roofline kernel):
 //   one workgroup = 4 waves x 32 queries of one (item, head); K / V tiles of 64 keys staged global -> registers -> LDS, the
-//   next tile's global loads in flight while the current tile is consumed;
-//   S^T = K Q^T with SWAPPED operands (v_mfma_f32_32x32x16_bf16 / _f16: A = K fragment, B = Q fragment kept in registers), so a lane
-//   owns ONE query and 16 of a 32-key sub-block's scores: scale, mask, running max / sum are lane-local, the two half-waves
-//   exchange one value per tile (v_permlane32_swap);
-//   O^T += V^T P^T: B = P^T is the exp'ed S^T accumulator packed to bf16 / fp16 (its C-layout key order is adopted as the MFMA k
-//   order), A = V^T fragments by ds_read_b64_tr_b16 from a row-major V tile in the blocked image [d/32][key/4][4 keys][32 d].
-//   fp32 softmax in the exp2 domain; scores are scaled in fp32 (q is NOT pre-rounded with the scale).
+//   next tile's global loads in flight while the current tile is consumed.
+// This file holds what is the general kernel's own: the 16-bit Q / K front end (v_mfma_f32_32x32x16_bf16 / _f16), the scale in
+// fp32 (q is NOT pre-rounded with the scale), masks and `causal`.  From the row max on — online softmax in the exp2 domain, P
+// packed to bf16 / fp16, O^T += V^T P^T, the epilogue — it runs the steps it shares with attention_sage.hip (attention_common.h).
 // Rows whose every key is masked produce zeros (torch's math path yields NaN there, its fused paths zeros).
 // Roofline: MFMA-bound, 4 * S_q * S_k * dh flop per (item, head); measured numbers in DESIGN.md (kernel table).
-#include "common.h"
+#include "attention_common.h"
 
 namespace {
 
 constexpr int GQ_WAVES = 4;
 constexpr int GQBLK = 32 * GQ_WAVES;   // queries per workgroup
-constexpr int GKV = 64;                // keys per tile
-
-typedef __attribute__((ext_vector_type(4))) short g_s16x4_t;
-typedef __attribute__((address_space(3))) g_s16x4_t g_lds_s16x4;
-
-// The element type of q / k / v / out (omni_attn_params.elem_type): the 8-element MFMA fragment, the 32x32x16 MFMA and the
-// round-to-nearest-even pack of two fp32 values.  Everything else of the kernel (addresses, softmax, masks) is type-blind.
-template <bool F16>
-struct g_elem;
-template <>
-struct g_elem<false> {
-  typedef bf16x8_t frag;
-  static OMNI_DEVINL f32x16_t mfma(frag a, frag b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-  static OMNI_DEVINL uint32_t pack2(float lo, float hi) { return pack_bf16x2(lo, hi); }
-};
-template <>
-struct g_elem<true> {
-  typedef f16x8_t frag;
-  static OMNI_DEVINL f32x16_t mfma(frag a, frag b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-  static OMNI_DEVINL uint32_t pack2(float lo, float hi) { return pack_f16x2(lo, hi); }
-};
-
-template <typename FRAG>
-OMNI_DEVINL FRAG g_tr_read_pair(uint32_t a, uint32_t b) {
-  g_s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((g_lds_s16x4*)(uintptr_t)a);
-  g_s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((g_lds_s16x4*)(uintptr_t)b);
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-  s16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(FRAG, v);
-}
-OMNI_DEVINL float g_xhalf_max(float x) {
-  uint32_t a = __builtin_bit_cast(uint32_t, x), b = a;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-  return fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
-}
-OMNI_DEVINL float g_xhalf_sum(float x) {
-  uint32_t a = __builtin_bit_cast(uint32_t, x), b = a;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-  return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
-}
+constexpr int GKV = ATTN_KV;           // keys per tile
 
 // F16: q / k / v / out are IEEE fp16 and both products run on v_mfma_f32_32x32x16_f16; P and the output are rounded to fp16
 // (nearest even).  P = exp2(s - m) <= 1 goes to the MFMA as it is, also where it is an fp16 SUBNORMAL (below 6.1e-5): measured,
@@ -74,7 +33,7 @@ OMNI_DEVINL float g_xhalf_sum(float x) {
 // mass: DESIGN.md kernel table, tests/test_gpu_attention_fp16.py flat tail), so no exponent shift of P is needed.
 template <int DH, bool F16>
 __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const omni_attn_params P, int qblocks) {
-  typedef g_elem<F16> E;
+  typedef attn_elem<F16> E;
   typedef typename E::frag frag_t;
   constexpr int NCH = DH / 8;              // 16-byte chunks per K / V row
   constexpr int ROWB = DH * 2;             // bytes per K row in LDS
@@ -111,7 +70,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
 #pragma unroll
     for (int i = 0; i < 16; ++i) o[d][i] = 0.0f;
   float m_run = -INFINITY, l_run = 0.0f;
-  const float sl2 = P.softmax_scale * 1.4426950408889634f;
+  const float sl2 = P.softmax_scale * OMNI_LOG2E;
 
   // keys this workgroup has to visit: all of them, or (causal) those up to its last query
   int k_end = k_len;
@@ -122,30 +81,18 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
   const uint16_t* vbase = P.v + (int64_t)k_start * P.ldv + hk * DH;
   u32x4_t kreg[NLD], vreg[NLD];
   auto load_tile = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = tid + i * (GQ_WAVES * 64);
-      const int key = min(t * GKV + c / NCH, k_len - 1), ch = c % NCH;      // keys past the end: re-read the last one (masked below)
-      kreg[i] = *reinterpret_cast<const u32x4_t*>(kbase + (int64_t)key * P.ldk + ch * 8);
-      vreg[i] = *reinterpret_cast<const u32x4_t*>(vbase + (int64_t)key * P.ldv + ch * 8);
-    }
+    attn_load_tile<ROWB, GQ_WAVES * 64>(kreg, kbase, P.ldk, t, k_len, tid);
+    attn_load_tile<ROWB, GQ_WAVES * 64>(vreg, vbase, P.ldv, t, k_len, tid);
   };
   auto store_tile = [&]() {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = tid + i * (GQ_WAVES * 64);
-      const int key = c / NCH, ch = c % NCH;
-      // K: row-major [64][DH], 16-B chunk index XOR (key & (NCH-1)): conflict-free ds_read_b128 of 32 keys at one logical chunk
-      *reinterpret_cast<u32x4_t*>(smem + key * ROWB + ((ch ^ (key & (NCH - 1))) << 4)) = kreg[i];
-      // V: [d/32][key/4][4 keys][32 d]: a tr-read's 16-lane group covers 4 keys x 16 d
-      *reinterpret_cast<u32x4_t*>(smem + K_BYTES + (ch >> 2) * 4096 + (key >> 2) * 256 + (key & 3) * 64 + (ch & 3) * 16) = vreg[i];
-    }
+    attn_store_tile<ROWB, GQ_WAVES * 64, false>(smem, kreg, tid);
+    attn_store_tile<ROWB, GQ_WAVES * 64, true>(smem + K_BYTES, vreg, tid);
   };
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
   uint32_t k_addr[NKS];
 #pragma unroll
-  for (int ks = 0; ks < NKS; ++ks) k_addr[ks] = lds0 + l31 * ROWB + ((((uint32_t)(ks * 2 + hi)) ^ (l31 & (NCH - 1))) << 4);
-  const uint32_t v_addr = lds0 + K_BYTES + ((lane & 15) >> 2) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8 + hi * 256;
+  for (int ks = 0; ks < NKS; ++ks) k_addr[ks] = attn_k_frag_addr<ROWB>(lds0, lane, ks);
+  const uint32_t v_addr = attn_vt_lane_addr(lds0 + K_BYTES, lane);
 
   const char* mrow = nullptr;              // this lane's mask row (element (b, h, qi, 0))
   const int msz = P.mask_type == 1 ? 1 : (P.mask_type == 2 ? 2 : 4);
@@ -172,7 +119,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
         s[j] = E::mfma(kf, qf[ks], s[j]);
       }
     }
-    // ---- scale, mask, online softmax.  register r of sub-block j <-> key t*64 + 32 j + (r & 3) + 8 (r >> 2) + 4 hi
+    // ---- scale and mask (register r of sub-block j <-> key attn_key_of(kv0, j, r, hi))
     const int kv0 = t * GKV;
     // which tiles need per-element work: the ragged last tile; with `causal` only the tiles that reach past this WAVE's smallest
     // query index (everything before the diagonal is attended as it is); with a mask every tile
@@ -195,7 +142,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-          const int kb = kv0 + j * 32 + 8 * rq + 4 * hi;                 // first of this lane's four consecutive keys
+          const int kb = attn_key_of(kv0, j, 4 * rq, hi);               // first of this lane's four consecutive keys
           float add[4] = {0.f, 0.f, 0.f, 0.f};
           bool ok[4];
 #pragma unroll
@@ -231,46 +178,13 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
           }
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float x = ok[e] ? s[j][rq * 4 + e] * sl2 + add[e] * 1.4426950408889634f : -INFINITY;
+            const float x = ok[e] ? s[j][rq * 4 + e] * sl2 + add[e] * OMNI_LOG2E : -INFINITY;
             s[j][rq * 4 + e] = x;
             mx = fmaxf(mx, x);
           }
         }
     }
-    mx = g_xhalf_max(mx);
-    const float m_new = fmaxf(m_run, mx);
-    const float m_use = m_new == -INFINITY ? 0.0f : m_new;   // nothing attendable so far: every p below is exp2(-inf) = 0
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
-    m_run = m_new;
-    float psum = 0.0f;
-    uint32_t pk[2][2][4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const float p0 = __builtin_amdgcn_exp2f(s[j][r] - m_use), p1 = __builtin_amdgcn_exp2f(s[j][r + 1] - m_use);
-        psum += p0 + p1;
-        pk[j][r >> 3][(r >> 1) & 3] = E::pack2(p0, p1);
-      }
-    l_run = l_run * alpha + psum;
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) o[d][i] *= alpha;
-    // ---- O^T += V^T P^T: four 16-key steps (sub-block j, half hf) x NDB 32-row blocks of d
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const u32x4_t p4 = {pk[j][hf][0], pk[j][hf][1], pk[j][hf][2], pk[j][hf][3]};
-        const frag_t pf = __builtin_bit_cast(frag_t, p4);
-#pragma unroll
-        for (int d = 0; d < NDB; ++d) {
-          const uint32_t va = v_addr + d * 4096 + (j * 8 + hf * 4) * 256;
-          const frag_t vf = g_tr_read_pair<frag_t>(va, va + 512);
-          o[d] = E::mfma(vf, pf, o[d]);
-        }
-      }
+    attn_softmax_pv_tile<E>(s, mx, v_addr, m_run, l_run, o);
     __syncthreads();                                         // every wave is done with tile t
     if (t + 1 < ntiles) {
       store_tile();
@@ -278,21 +192,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void flash_attn_general_kernel(const
     }
   }
 
-  // ---- epilogue: lane (query l31, half hi), register r of block d <-> channel 32 d + (r & 3) + 8 (r >> 2) + 4 hi
-  const float l = g_xhalf_sum(l_run);
-  const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-  if (qi < q_len) {
-    uint16_t* op = P.out + (int64_t)(q_start + qi) * P.ldo + h * DH + hi * 4;
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        u32x2_t w;
-        w[0] = E::pack2(o[d][qd * 4 + 0] * inv, o[d][qd * 4 + 1] * inv);
-        w[1] = E::pack2(o[d][qd * 4 + 2] * inv, o[d][qd * 4 + 3] * inv);
-        *reinterpret_cast<u32x2_t*>(op + d * 32 + qd * 8) = w;
-      }
-  }
+  attn_store_out<E>(o, l_run, P.out, P.ldo, 0, q_start + qi, h, hi, qi < q_len);   // (out_k32_rows != 0 is rejected at validation)
 }
 
 template <int DH, bool F16>

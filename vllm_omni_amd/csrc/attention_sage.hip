@@ -11,46 +11,27 @@
 // Host model of the same steps: tests/_sage_model.py.
 //
 // Launches: sage_kmean_kernel (K mean), sage_quant_kernel twice (Q, K' -> int8 + block scales, into a caller-owned workspace),
-// sage_attn_fwd_kernel.  The attention kernel keeps attention_general.hip's structure with hipcc scheduling the loop: one
-// workgroup = 4 waves x 32 queries of one (item, head); 64-key tiles (= one K scale block) staged global -> registers -> LDS
-// with the next tile's loads in flight; S^T = K Q^T with swapped operands so a lane owns one query — here with
-// v_mfma_i32_32x32x32_i8 (A = K fragment from LDS, B = the lane's int8 Q fragment, 16 bytes per k-step, kept in registers: half
-// the registers of the bf16 Q); the int32 scores are converted and scaled by sq (per lane: one query) * sk (per tile) inside the
-// softmax; O^T += V^T P^T exactly as the general kernel (bf16 MFMA, V^T by ds_read_b64_tr_b16).  The MFMA k order inside a
-// fragment does not matter for Q K^T: both operands are loaded with the same channel map and the product sums over all of it.
+// sage_attn_fwd_kernel.  The attention kernel has attention_general.hip's structure (one workgroup = 4 waves x 32 queries of one
+// (item, head); 64-key tiles (= one K scale block) staged global -> registers -> LDS with the next tile's loads in flight; hipcc
+// schedules the loop) and shares everything from the row max on with it (attention_common.h: online softmax, bf16 P V MFMA with
+// V^T by transposed reads, epilogue).  Its own is the front end: S^T = K Q^T with swapped operands on v_mfma_i32_32x32x32_i8
+// (A = K fragment from the int8 K image — the shared K image at a row pitch of DH bytes —, B = the lane's int8 Q fragment, 16
+// bytes per k-step, kept in registers: half the registers of the bf16 Q); the int32 scores are converted and scaled by sq (per
+// lane: one query) * sk (per tile).  The MFMA k order inside a fragment does not matter for Q K^T: both operands are loaded with
+// the same channel map and the product sums over all of it.
 // Every launch honours an optional per-item skip predicate (TeaCache, omni_dit_forward): a skipped item costs nothing and its
 // output rows are left untouched.
-#include "common.h"
+#include "attention_common.h"
 
 namespace {
 
 constexpr int SQ_WAVES = 4;
 constexpr int SQBLK = 32 * SQ_WAVES;   // queries per workgroup (two 64-row scale blocks)
-constexpr int SKV = 64;                // keys per tile = rows per scale block
+constexpr int SKV = ATTN_KV;           // keys per tile = rows per scale block
 constexpr int SBLK = 64;
 
 typedef __attribute__((ext_vector_type(4))) int i32x4_t;
 typedef __attribute__((ext_vector_type(16))) int i32x16_t;
-typedef __attribute__((ext_vector_type(4))) short s_s16x4_t;
-typedef __attribute__((address_space(3))) s_s16x4_t s_lds_s16x4;
-
-OMNI_DEVINL bf16x8_t s_tr_read_pair(uint32_t a, uint32_t b) {
-  s_s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s_lds_s16x4*)(uintptr_t)a);
-  s_s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s_lds_s16x4*)(uintptr_t)b);
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-  s16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-OMNI_DEVINL float s_xhalf_max(float x) {
-  uint32_t a = __builtin_bit_cast(uint32_t, x), b = a;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-  return fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
-}
-OMNI_DEVINL float s_xhalf_sum(float x) {
-  uint32_t a = __builtin_bit_cast(uint32_t, x), b = a;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-  return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
-}
 
 // Workspace carve: every piece 256-byte aligned.  int8 rows are indexed (item, row within the item), so the layout depends on the
 // host-known bounds only (B, max_seqlen), never on the device cu_seqlens.
@@ -177,14 +158,13 @@ template <int DH>
 __global__ __launch_bounds__(SQ_WAVES * 64, 2) void sage_attn_fwd_kernel(const omni_attn_params P, SageWs W, int qblocks,
                                                                       const int32_t* __restrict__ item_skip) {
   constexpr int KROW = DH;                 // bytes per int8 K row in LDS
-  constexpr int NCK = DH / 16;             // 16-byte chunks per int8 K row
-  constexpr int NCV = DH / 8;              // 16-byte chunks per bf16 V row
   constexpr int NKS = DH / 32;             // i8 MFMA k-steps of the QK^T product
   constexpr int NDB = DH / 32;             // 32-row blocks of O^T
   constexpr int K_BYTES = SKV * KROW;
   constexpr int V_BYTES = SKV * DH * 2;
-  constexpr int NLK = SKV * NCK / (SQ_WAVES * 64);   // 16-byte K pieces per thread per tile (2 at dh 128, 1 at dh 64)
-  constexpr int NLV = SKV * NCV / (SQ_WAVES * 64);   // 16-byte V pieces per thread per tile (4 / 2)
+  constexpr int NLK = K_BYTES / 16 / (SQ_WAVES * 64);   // 16-byte K pieces per thread per tile (2 at dh 128, 1 at dh 64)
+  constexpr int NLV = V_BYTES / 16 / (SQ_WAVES * 64);   // 16-byte V pieces per thread per tile (4 / 2)
+  typedef attn_elem<false> E;              // P, V and the output are bf16
   __shared__ __attribute__((aligned(16))) char smem[K_BYTES + V_BYTES];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -225,40 +205,18 @@ __global__ __launch_bounds__(SQ_WAVES * 64, 2) void sage_attn_fwd_kernel(const o
   const int64_t ld8k = (int64_t)P.H_kv * DH;
   u32x4_t kreg[NLK], vreg[NLV];
   auto load_tile = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < NLK; ++i) {
-      const int c = tid + i * (SQ_WAVES * 64);
-      const int key = min(t * SKV + c / NCK, k_len - 1), ch = c % NCK;     // keys past the end: re-read the last one (masked below)
-      kreg[i] = *reinterpret_cast<const u32x4_t*>(kbase + (int64_t)key * ld8k + ch * 16);
-    }
-#pragma unroll
-    for (int i = 0; i < NLV; ++i) {
-      const int c = tid + i * (SQ_WAVES * 64);
-      const int key = min(t * SKV + c / NCV, k_len - 1), ch = c % NCV;
-      vreg[i] = *reinterpret_cast<const u32x4_t*>(vbase + (int64_t)key * P.ldv + ch * 8);
-    }
+    attn_load_tile<KROW, SQ_WAVES * 64>(kreg, kbase, ld8k, t, k_len, tid);
+    attn_load_tile<2 * DH, SQ_WAVES * 64>(vreg, vbase, P.ldv, t, k_len, tid);
   };
   auto store_tile = [&]() {
-#pragma unroll
-    for (int i = 0; i < NLK; ++i) {
-      const int c = tid + i * (SQ_WAVES * 64);
-      const int key = c / NCK, ch = c % NCK;
-      // K: row-major [64][DH] int8, 16-B chunk index XOR (key & (NCK-1)): 32 keys at one logical chunk spread over the banks
-      *reinterpret_cast<u32x4_t*>(smem + key * KROW + ((ch ^ (key & (NCK - 1))) << 4)) = kreg[i];
-    }
-#pragma unroll
-    for (int i = 0; i < NLV; ++i) {
-      const int c = tid + i * (SQ_WAVES * 64);
-      const int key = c / NCV, ch = c % NCV;
-      // V: [d/32][key/4][4 keys][32 d] (attention_general.hip): a tr-read's 16-lane group covers 4 keys x 16 d
-      *reinterpret_cast<u32x4_t*>(smem + K_BYTES + (ch >> 2) * 4096 + (key >> 2) * 256 + (key & 3) * 64 + (ch & 3) * 16) = vreg[i];
-    }
+    attn_store_tile<KROW, SQ_WAVES * 64, false>(smem, kreg, tid);
+    attn_store_tile<2 * DH, SQ_WAVES * 64, true>(smem + K_BYTES, vreg, tid);
   };
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
   uint32_t k_addr[NKS];
 #pragma unroll
-  for (int ks = 0; ks < NKS; ++ks) k_addr[ks] = lds0 + l31 * KROW + ((((uint32_t)(ks * 2 + hi)) ^ (l31 & (NCK - 1))) << 4);
-  const uint32_t v_addr = lds0 + K_BYTES + ((lane & 15) >> 2) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8 + hi * 256;
+  for (int ks = 0; ks < NKS; ++ks) k_addr[ks] = attn_k_frag_addr<KROW>(lds0, lane, ks);
+  const uint32_t v_addr = attn_vt_lane_addr(lds0 + K_BYTES, lane);
 
   if (ntiles > 0) {
     load_tile(0);
@@ -280,8 +238,7 @@ __global__ __launch_bounds__(SQ_WAVES * 64, 2) void sage_attn_fwd_kernel(const o
         si[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf, qf[ks], si[j], 0, 0, 0);
       }
     }
-    // ---- dequantise (sq of this lane's query x sk of this tile), online softmax.  register r of sub-block j <-> key
-    // t*64 + 32 j + (r & 3) + 8 (r >> 2) + 4 hi
+    // ---- dequantise (sq of this lane's query x sk of this tile); the ragged last tile masks its keys past k_len
     const float scl = sq * skp[(int64_t)t * P.H_kv];
     const int kv0 = t * SKV;
     f32x16_t s[2];
@@ -299,44 +256,11 @@ __global__ __launch_bounds__(SQ_WAVES * 64, 2) void sage_attn_fwd_kernel(const o
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = kv0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          s[j][r] = key < k_len ? (float)si[j][r] * scl : -INFINITY;
+          s[j][r] = attn_key_of(kv0, j, r, hi) < k_len ? (float)si[j][r] * scl : -INFINITY;
           mx = fmaxf(mx, s[j][r]);
         }
     }
-    mx = s_xhalf_max(mx);
-    const float m_new = fmaxf(m_run, mx);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-    m_run = m_new;
-    float psum = 0.0f;
-    uint32_t pk[2][2][4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const float p0 = __builtin_amdgcn_exp2f(s[j][r] - m_new), p1 = __builtin_amdgcn_exp2f(s[j][r + 1] - m_new);
-        psum += p0 + p1;
-        pk[j][r >> 3][(r >> 1) & 3] = pack_bf16x2(p0, p1);
-      }
-    l_run = l_run * alpha + psum;
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) o[d][i] *= alpha;
-    // ---- O^T += V^T P^T: four 16-key steps (sub-block j, half hf) x NDB 32-row blocks of d
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const u32x4_t p4 = {pk[j][hf][0], pk[j][hf][1], pk[j][hf][2], pk[j][hf][3]};
-        const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, p4);
-#pragma unroll
-        for (int d = 0; d < NDB; ++d) {
-          const uint32_t va = v_addr + d * 4096 + (j * 8 + hf * 4) * 256;
-          const bf16x8_t vf = s_tr_read_pair(va, va + 512);
-          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[d], 0, 0, 0);
-        }
-      }
+    attn_softmax_pv_tile<E>(s, mx, v_addr, m_run, l_run, o);
     __syncthreads();                                         // every wave is done with tile t
     if (t + 1 < ntiles) {
       store_tile();
@@ -344,25 +268,7 @@ __global__ __launch_bounds__(SQ_WAVES * 64, 2) void sage_attn_fwd_kernel(const o
     }
   }
 
-  // ---- epilogue: lane (query l31, half hi), register r of block d <-> channel 32 d + (r & 3) + 8 (r >> 2) + 4 hi
-  const float l = s_xhalf_sum(l_run);
-  const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-  const int64_t row = q_start + qi;
-  if (qi < q_len && (P.out_k32_rows == 0 || row < P.out_k32_rows)) {      // a K32-blocked output holds out_k32_rows rows
-#pragma unroll
-    for (int d = 0; d < NDB; ++d) {
-      // row-major [rows][ldo], or K32-blocked [H * DH / 32][R][32] (what the out-projection GEMM's A operand reads)
-      uint16_t* op = P.out_k32_rows > 0 ? P.out + (((int64_t)h * NDB + d) * P.out_k32_rows + row) * 32 + hi * 4
-                                        : P.out + row * P.ldo + h * DH + d * 32 + hi * 4;
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        u32x2_t w;
-        w[0] = pack_bf16x2(o[d][qd * 4 + 0] * inv, o[d][qd * 4 + 1] * inv);
-        w[1] = pack_bf16x2(o[d][qd * 4 + 2] * inv, o[d][qd * 4 + 3] * inv);
-        *reinterpret_cast<u32x2_t*>(op + qd * 8) = w;
-      }
-    }
-  }
+  attn_store_out<E>(o, l_run, P.out, P.ldo, P.out_k32_rows, q_start + qi, h, hi, qi < q_len);
 }
 
 template <int DH>
@@ -372,7 +278,7 @@ int launch_sage(const omni_attn_params* p, const SageWs& w, const int32_t* item_
   const int qblocks = (p->max_seqlen_q + SQBLK - 1) / SQBLK;
   const long g_attn = (long)p->B * p->H * qblocks;
   if (g_q > 0x7fffffffL || g_k > 0x7fffffffL || g_attn > 0x7fffffffL) return OMNI_ERR_UNSUPPORTED;
-  const float mul = q_prescaled ? 1.0f : p->softmax_scale * 1.4426950408889634f;
+  const float mul = q_prescaled ? 1.0f : p->softmax_scale * OMNI_LOG2E;
   hipLaunchKernelGGL((sage_kmean_kernel<DH>), dim3((unsigned)g_mean), dim3(256), 0, s, p->k, p->ldk, p->cu_seqlens_k, p->H_kv,
                      item_skip, w.km);
   OMNI_CHECK_LAUNCH();

@@ -33,7 +33,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "attention_common.h"
 
 namespace {
 
@@ -129,12 +129,6 @@ template <int KA, int OFF>  // one K fragment (16 B per lane) LDS -> AGPRs
 OMNI_DEVINL void kread(uint32_t addr) {
   asm volatile("ds_read_b128 a[%c1:%c2], %0 offset:%c3" ::"v"(addr), "i"(KA), "i"(KA + 3), "i"(OFF));
 }
-template <int OFF>
-OMNI_DEVINL u32x2_t vread8(uint32_t addr) {   // ds_read_b64_tr_b16: hardware 4x4 transpose read (half of a V^T fragment)
-  u32x2_t v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%c2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
 template <int A>
 OMNI_DEVINL void agpr_write(uint32_t v) { asm volatile("v_accvgpr_write_b32 a[%c1], %0" ::"v"(v), "i"(A)); }
 template <int A>
@@ -177,15 +171,12 @@ OMNI_DEVINL void max3x4_first(float& m0, float& m1, float a0, float a1, float a2
   asm volatile("v_max3_f32 %0, %2, %3, %4\n\tv_max3_f32 %1, %6, %7, %8\n\tv_max_f32 %0, %0, %5\n\tv_max_f32 %1, %1, %9"
                : "=&v"(m0), "=&v"(m1) : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "v"(b2), "v"(b3));
 }
-OMNI_DEVINL float xhalf_max(float x) {          // max(x, x of the lane 32 away): one statement, 5 issue slots
+// xhalf_max of attention_common.h as ONE statement of 5 issue slots, hand-padded: it sits in an MFMA gap of P2, where the
+// compiler would pad the shared form's fmaxf on asm outputs.  (xhalf_sum runs once, in the epilogue: the shared one.)
+OMNI_DEVINL float xhalf_max_1stmt(float x) {
   float a = x, b;
   asm volatile("v_mov_b32 %1, %0\n\ts_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1\n\tv_max_f32 %0, %0, %1" : "+v"(a), "=&v"(b));
   return a;
-}
-OMNI_DEVINL float xhalf_sum(float x) {
-  uint32_t a = __builtin_bit_cast(uint32_t, x), b = a;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-  return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
 }
 // LDS-DMA through a buffer descriptor: per-lane byte offset (offen) + uniform soffset; M0 = LDS byte address of the 1-KiB
 // piece (the hardware adds lane * 16).  Rows past the end of the sequence are outside the descriptor's range and land as
@@ -240,17 +231,14 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
 
-  // XCD-aware head-major block order (attention.hip): block b runs on XCD b % 8; every XCD gets a contiguous range of the
-  // (item*head, q-block) list, so the workgroups resident on an XCD stream the same few heads' K / V through its L2
+  // XCD-aware head-major block order (common.h omni_xcd_contiguous) over the (item*head, q-block) list of the full blocks
   int hb, qb, sp = 0;
   const int nfull = n_heads_total * qfull;          // == gridDim.x without split mode
   const bool split = (int)blockIdx.x >= nfull;
   if (!split) {
-    const int nwg = nfull, bid = blockIdx.x, qblocks = qfull;
-    const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-    hb = lid / qblocks;
-    qb = lid - hb * qblocks;
+    const int lid = omni_xcd_contiguous(blockIdx.x, nfull);
+    hb = lid / qfull;
+    qb = lid - hb * qfull;
   } else {
     const int r = (int)blockIdx.x - nfull;
     hb = r / nsplit;
@@ -301,7 +289,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
   const u32x4_t v_srd = make_srd(v + (int64_t)(seq_start + kv_row0) * ldv + h * DH, (uint32_t)((int64_t)(kv_rows - 1) * ldv * 2 + DH * 2));
   const int k_key0 = 4 * wave + (lane >> 4);
   const int v_key = 16 * wave + 4 * (lane >> 4) + ((lane >> 2) & 3);
-  const uint32_t k_src = (uint32_t)(k_key0 * ldk * 2) + (uint32_t)(((lane & 15) ^ (k_key0 & 15)) * 16);
+  const uint32_t k_src = (uint32_t)(k_key0 * ldk * 2) + attn_k_chunk<2 * DH>(k_key0, lane & 15) * 16;
   const uint32_t v_src = (uint32_t)(v_key * ldv * 2) + (uint32_t)((lane & 3) * 16);
   const uint32_t k_tile_stride = (uint32_t)(KVBLK * ldk * 2), v_tile_stride = (uint32_t)(KVBLK * ldv * 2);
   const uint32_t k_piece_stride = (uint32_t)(16 * ldk * 2);
@@ -378,11 +366,11 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
     agpr_zero_range<A_O>(std::make_integer_sequence<int, 128>{});
   }
 
-  // ---- fragment read addresses (attention.hip).  K: row key = j*32 + l31, chunk (ks*2 + hi) ^ (key & 15)
+  // ---- fragment read addresses (attention_common.h)
   uint32_t k_addr[8];
 #pragma unroll
-  for (int ks = 0; ks < 8; ++ks) k_addr[ks] = lds0 + K_SLOT0 + l31 * 256 + ((((uint32_t)(ks * 2 + hi)) ^ (l31 & 15)) << 4);
-  const uint32_t v_addr = lds0 + V_SLOT0 + ((lane & 15) >> 2) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8 + hi * 256;
+  for (int ks = 0; ks < 8; ++ks) k_addr[ks] = attn_k_frag_addr<2 * DH>(lds0 + K_SLOT0, lane, ks);
+  const uint32_t v_addr = attn_vt_lane_addr(lds0 + V_SLOT0, lane);
 
   float negm[2];
   f32x16_t negm16[2];
@@ -420,8 +408,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = kv0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        if (key >= kv_rows) { S[0][j][r] = -INFINITY; S[1][j][r] = -INFINITY; }
+        if (attn_key_of(kv0, j, r, hi) >= kv_rows) { S[0][j][r] = -INFINITY; S[1][j][r] = -INFINITY; }
       }
   };
   auto row_max = [&](f32x16_t (&S)[2][2], float (&mx)[2]) {
@@ -433,7 +420,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
         m = max3(m, S[bq][c >> 2][(c & 3) * 4 + 0], S[bq][c >> 2][(c & 3) * 4 + 1]);
         m = max3(m, S[bq][c >> 2][(c & 3) * 4 + 2], S[bq][c >> 2][(c & 3) * 4 + 3]);
       }
-      mx[bq] = xhalf_max(m);
+      mx[bq] = xhalf_max_1stmt(m);
     }
   };
 
@@ -494,7 +481,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
 
   auto vread = [&](auto ff) {
     constexpr int f = decltype(ff)::value;
-    constexpr int off = (f & 3) * 4096 + (((f >> 3) * 8 + ((f >> 2) & 1) * 4) * 256);
+    constexpr int off = attn_pv_off(f & 3, f >> 3, (f >> 2) & 1);
     if constexpr (OMNI_W64_ABL & 8) {
       const uint32_t va_ = va;
       u32x2_t a_, b_;
@@ -502,8 +489,8 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
       asm volatile("" : "=v"(b_) : "v"(va_));
       vlo[f & 3] = a_; vhi[f & 3] = b_;
     } else {
-      vlo[f & 3] = vread8<off>(va);
-      vhi[f & 3] = vread8<off + 512>(va);
+      vlo[f & 3] = tr_read8<off>(va);
+      vhi[f & 3] = tr_read8<off + 512>(va);
     }
   };
 
@@ -606,8 +593,8 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
           max3x4(mx[0], mx[1], SN[0][c >> 2][(c & 3) * 4 + 0], SN[0][c >> 2][(c & 3) * 4 + 1], SN[0][c >> 2][(c & 3) * 4 + 2],
                  SN[0][c >> 2][(c & 3) * 4 + 3], SN[1][c >> 2][(c & 3) * 4 + 0], SN[1][c >> 2][(c & 3) * 4 + 1],
                  SN[1][c >> 2][(c & 3) * 4 + 2], SN[1][c >> 2][(c & 3) * 4 + 3]);
-        if constexpr (f == 10 && OMNI_W64_XHALF_IN_P2) mxn[0] = xhalf_max(mx[0]);
-        if constexpr (f == 11 && OMNI_W64_XHALF_IN_P2) mxn[1] = xhalf_max(mx[1]);
+        if constexpr (f == 10 && OMNI_W64_XHALF_IN_P2) mxn[0] = xhalf_max_1stmt(mx[0]);
+        if constexpr (f == 11 && OMNI_W64_XHALF_IN_P2) mxn[1] = xhalf_max_1stmt(mx[1]);
         if constexpr (f == 12 && OMNI_W64_XHALF_IN_P2 && OMNI_W64_EARLYDEC) rescale = !__all(max3(mxn[0], mxn[0], mxn[1]) <= DEFER);
       }
     };
@@ -653,8 +640,8 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fwd_w64_kernel(
     [&]<int... F>(std::integer_sequence<int, F...>) { (p2_step(ic<F>{}), ...); }(std::make_integer_sequence<int, 16>{});
     __builtin_amdgcn_s_setprio(0);
     if constexpr (HAS_NEXT && !OMNI_W64_XHALF_IN_P2) {
-      mxn[0] = xhalf_max(mx[0]);
-      mxn[1] = xhalf_max(mx[1]);
+      mxn[0] = xhalf_max_1stmt(mx[0]);
+      mxn[1] = xhalf_max_1stmt(mx[1]);
       if constexpr (OMNI_W64_EARLYDEC) rescale = !__all(max3(mxn[0], mxn[0], mxn[1]) <= DEFER);
     }
     if constexpr (!(OMNI_W64_ABL & 2)) {
@@ -832,37 +819,29 @@ int omni_internal_flash_attn_w64(const omni_bf16* q, const omni_bf16* k, const o
     return hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_w64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                LDS_BYTES) == hipSuccess;
   }));
-  const int qblocks = (max_seqlen + QBLK - 1) / QBLK;
   const int nh = B * H;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // items of unequal length: the compact head-major slot grid where it is smaller (common.h: the rule and why).  The key-range
-  // split of the short last q-block is off in this mode: its makespan model assumes one sequence length
-  if (const int slots = omni_attn_compact_slots(total_rows, B, max_seqlen, QBLK)) {
-    hipLaunchKernelGGL(flash_attn_fwd_w64_kernel, dim3(H * slots), dim3(256), LDS_BYTES, s, q, k, v, out, ldq, ldk, ldv, ldo,
-                       cu_seqlens, H, H, softmax_scale * 1.4426950408889634f, out_k32_rows, item_skip, q_prescaled, slots, 1,
-                       nullptr, nullptr, B);
-    OMNI_CHECK_LAUNCH();
-    return OMNI_OK;
-  }
+  // The grid: (n_heads_total, qfull) full-block list + n_heads_total * nsplit split workgroups behind it (nsplit > 1 only).
+  //   items of unequal length: the compact head-major slot grid where it is smaller (common.h: the rule and why).  The key-range
+  //   split of the short last q-block is off in this mode: its makespan model assumes one sequence length;
+  //   else, with a workspace, the split of the short last q-block where the makespan model says it pays;
+  //   else every q-block of every (item, head) as a full block.
+  const int slots = omni_attn_compact_slots(total_rows, B, max_seqlen, QBLK);
   int nsplit = 1;
-  if (part_ws && (reinterpret_cast<uintptr_t>(part_ws) & 15) == 0)
+  if (!slots && part_ws && (reinterpret_cast<uintptr_t>(part_ws) & 15) == 0)
     nsplit = w64_split_factor(nh, max_seqlen / QBLK, max_seqlen, omni_num_cus(), part_ws_bytes);
+  const int n_heads_total = slots ? H : nh;
+  const int qfull = slots ? slots : nsplit > 1 ? max_seqlen / QBLK : (max_seqlen + QBLK - 1) / QBLK;
+  float* part_o = nsplit > 1 ? static_cast<float*>(part_ws) : nullptr;
+  float* part_ml = nsplit > 1 ? part_o + (size_t)nh * nsplit * 64 * DH : nullptr;
+  hipLaunchKernelGGL(flash_attn_fwd_w64_kernel, dim3(n_heads_total * qfull + (nsplit > 1 ? nh * nsplit : 0)), dim3(256), LDS_BYTES, s,
+                     q, k, v, out, ldq, ldk, ldv, ldo, cu_seqlens, n_heads_total, H, softmax_scale * OMNI_LOG2E, out_k32_rows, item_skip,
+                     q_prescaled, qfull, nsplit, part_o, part_ml, slots ? B : 0);
+  OMNI_CHECK_LAUNCH();
   if (nsplit > 1) {
-    const int qfull = max_seqlen / QBLK;
-    float* part_o = static_cast<float*>(part_ws);
-    float* part_ml = part_o + (size_t)nh * nsplit * 64 * DH;
-    hipLaunchKernelGGL(flash_attn_fwd_w64_kernel, dim3(nh * qfull + nh * nsplit), dim3(256), LDS_BYTES, s, q, k, v, out, ldq, ldk,
-                       ldv, ldo, cu_seqlens, nh, H, softmax_scale * 1.4426950408889634f, out_k32_rows, item_skip, q_prescaled, qfull,
-                       nsplit, part_o, part_ml, 0);
-    OMNI_CHECK_LAUNCH();
     hipLaunchKernelGGL(attn_split_combine_kernel, dim3(nh), dim3(256), 0, s, out, ldo, out_k32_rows, cu_seqlens, H, qfull, nsplit,
                        part_o, part_ml, item_skip);
     OMNI_CHECK_LAUNCH();
-    return OMNI_OK;
   }
-  hipLaunchKernelGGL(flash_attn_fwd_w64_kernel, dim3(nh * qblocks), dim3(256), LDS_BYTES, s, q, k, v, out, ldq, ldk, ldv, ldo,
-                     cu_seqlens, nh, H, softmax_scale * 1.4426950408889634f, out_k32_rows, item_skip, q_prescaled, qblocks, 1,
-                     nullptr, nullptr, 0);
-  OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }

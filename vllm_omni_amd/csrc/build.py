@@ -222,7 +222,8 @@ def check_agpr_ownership(src: str, verbose: bool = True) -> None:
 def build(force: bool = False, verbose: bool = True) -> str:
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(HERE, "common.h"), os.path.join(HERE, "..", "..", "include", "omni_cdna4.h")]
+    headers = [os.path.join(HERE, "common.h"), os.path.join(HERE, "attention_common.h"),
+               os.path.join(HERE, "..", "..", "include", "omni_cdna4.h")]
     srcs = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
     objs = [os.path.join(objdir, os.path.basename(s)[:-4] + ".o") for s in srcs]
 

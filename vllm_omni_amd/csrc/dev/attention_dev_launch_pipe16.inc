@@ -31,7 +31,7 @@ int launch_pipe16(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, om
   const int qblocks = (max_seqlen + 32 * NW - 1) / (32 * NW);
   const int nh = B * H;
   hipLaunchKernelGGL((flash_attn_fwd_pipe16_kernel<NW>), dim3(nh * qblocks), dim3(NW * 64), LDS_BYTES, s, q, k, v, out, ldq,
-                     ldk, ldv, ldo, cu_seqlens, nh, H, softmax_scale * 1.4426950408889634f, out_k32_rows, attn_block_order(), item_skip);
+                     ldk, ldv, ldo, cu_seqlens, nh, H, softmax_scale * OMNI_LOG2E, out_k32_rows, attn_block_order(), item_skip);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }

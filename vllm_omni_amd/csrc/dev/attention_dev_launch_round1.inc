@@ -15,7 +15,7 @@ int launch_attn(const omni_bf16* q, const omni_bf16* k, const omni_bf16* v, omni
   const int qblocks = (max_seqlen + QBLK - 1) / QBLK;
   const int nh = B * H;
   hipLaunchKernelGGL(flash_attn_fwd_kernel<NQ>, dim3(nh * qblocks), dim3(NWAVES * 64), LDS_BYTES, s, q, k, v, out, ldq,
-                     ldk, ldv, ldo, cu_seqlens, nh, H, softmax_scale * 1.4426950408889634f);
+                     ldk, ldv, ldo, cu_seqlens, nh, H, softmax_scale * OMNI_LOG2E);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }

@@ -76,8 +76,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void flash_attn_fwd_pip
   int hb, qblk;                                  // block -> (item*head, q-block): see flash_attn_fwd_pipe_kernel
   if (block_order == 1) {
     const int nwg = gridDim.x, bid = blockIdx.x, qblocks = nwg / n_heads_total;
-    const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int lid = omni_xcd_contiguous(bid, nwg);
     hb = lid / qblocks;
     qblk = lid - hb * qblocks;
   } else {
@@ -311,16 +310,16 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void flash_attn_fwd_pip
 #define OMNI_VOFF(i) ((((i) & 7) >> 1) * 4096 + ((i) >> 3) * 2048)
 #define OMNI_VREAD(i)                                                                      \
   do {                                                                                     \
-    vlo[(i) & 3] = lds_tr_read8<OMNI_VOFF(i)>(((i) & 1) ? vb1 : vb0);                      \
-    vhi[(i) & 3] = lds_tr_read8<OMNI_VOFF(i) + 1024>(((i) & 1) ? vb1 : vb0);               \
+    vlo[(i) & 3] = tr_read8<OMNI_VOFF(i)>(((i) & 1) ? vb1 : vb0);                      \
+    vhi[(i) & 3] = tr_read8<OMNI_VOFF(i) + 1024>(((i) & 1) ? vb1 : vb0);               \
   } while (0)
 #else
       const uint32_t vb = lds0 + (t & 1) * STAGE_BYTES + v_lane_off;
 #define OMNI_VOFF(i) ((((i) & 7) >> 1) * 4096 + ((i) >> 3) * 2048 + ((i) & 1) * 256)
 #define OMNI_VREAD(i)                                                                      \
   do {                                                                                     \
-    vlo[(i) & 3] = lds_tr_read8<OMNI_VOFF(i)>(vb);                                         \
-    vhi[(i) & 3] = lds_tr_read8<OMNI_VOFF(i) + 1024>(vb);                                  \
+    vlo[(i) & 3] = tr_read8<OMNI_VOFF(i)>(vb);                                         \
+    vhi[(i) & 3] = tr_read8<OMNI_VOFF(i) + 1024>(vb);                                  \
   } while (0)
 #endif
 #define OMNI_PV(i)                                                                                             \

@@ -206,8 +206,8 @@ __global__ __launch_bounds__(NWAVES * 64, (NQ == 1 ? 2 : 1)) void flash_attn_fwd
 #define OMNI_VOFF(i) (((i) & 3) * 4096 + ((((i) >> 3) * 8 + (((i) >> 2) & 1) * 4) * 256))
 #define OMNI_VREAD(i)                                   \
   do {                                                  \
-    vlo[(i) & 3] = lds_tr_read8<OMNI_VOFF(i)>(vb);      \
-    vhi[(i) & 3] = lds_tr_read8<OMNI_VOFF(i) + 512>(vb); \
+    vlo[(i) & 3] = tr_read8<OMNI_VOFF(i)>(vb);      \
+    vhi[(i) & 3] = tr_read8<OMNI_VOFF(i) + 512>(vb); \
   } while (0)
 #define OMNI_PV(i)                                                                                             \
   do {                                                                                                         \

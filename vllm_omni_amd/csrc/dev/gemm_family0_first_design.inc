@@ -10,8 +10,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_kernel(const omni_gemm_
 
   // ---- tile id: XCD-aware bijective remap, then GROUP_M banding -------------------------------
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int lid = omni_xcd_contiguous(bid, nwg);
   const int band_sz = GROUP_M * tiles_n;
   const int band = lid / band_sz, in_band = lid - band * band_sz;
   const int first_m = band * GROUP_M;

@@ -34,8 +34,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp2_kernel(const omni_g
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nwg = tiles_m * tiles_n;
   const int bid = blockIdx.x;
-  const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int lid = omni_xcd_contiguous(bid, nwg);
   const int band_sz = GROUP_M * tiles_n;
   const int band = lid / band_sz, in_band = lid - band * band_sz;
   const int first_m = band * GROUP_M;
@@ -226,8 +225,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void gemm_bf16_w4_kernel(const omni_
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int lid = omni_xcd_contiguous(bid, nwg);
   const int band_sz = GROUP_M * tiles_n;
   const int band = lid / band_sz, in_band = lid - band * band_sz;
   const int first_m = band * GROUP_M;

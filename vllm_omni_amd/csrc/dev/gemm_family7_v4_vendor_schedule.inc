@@ -28,8 +28,7 @@ __global__ __launch_bounds__(Q4_THREADS, 1) void gemm_bf16_v4_kernel(const omni_
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nwg = tiles_m * tiles_n;
   const int bid = (int)blockIdx.x;
-  const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int lid = omni_xcd_contiguous(bid, nwg);
   const int band_sz = GROUP_M * tiles_n;
   const int band = lid / band_sz, in_band = lid - band * band_sz;
   const int first_m = band * GROUP_M;

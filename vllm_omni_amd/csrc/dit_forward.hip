@@ -260,7 +260,7 @@ int run_block(const omni_dit_weights* w, int l, const omni_dit_batch* b, const W
         p.g[g].qk_rope_cos = b->rope_cos; p.g[g].qk_rope_sin = b->rope_sin; p.g[g].qk_eps = eps;
         // the whole-block path hands q to the attention kernel pre-multiplied by softmax_scale * log2(e) (one rounding, as
         // before); a sequence-parallel caller (BLOCK_QKV) gets the reference's un-scaled q back
-        if (q_prescale) p.g[g].qk_q_scale = sm_scale * 1.4426950408889634f;
+        if (q_prescale) p.g[g].qk_q_scale = sm_scale * OMNI_LOG2E;
       }
     }
     p.g[0].a_k32_rows = bRi; p.g[1].a_k32_rows = bRt;

@@ -675,8 +675,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_ring_kernel(const omni_
   const int nwg = tiles_m * tiles_n;
 #pragma unroll 1
   for (int bid = blockIdx.x; bid < nwg; bid += gridDim.x) {
-  const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int lid = omni_xcd_contiguous(bid, nwg);
   const int band_sz = GROUP_M * tiles_n;
   const int band = lid / band_sz, in_band = lid - band * band_sz;
   const int first_m = band * GROUP_M;
@@ -1007,8 +1006,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp_kernel(const omni_ge
                                 : (tail ? tail_first + ((int)blockIdx.x - tail_first) / nsplit : (int)blockIdx.x);
   if (SPLITK == 3 && bid >= nwg) return;                                   // a pad block of the XCD-aligned grid
   const bool partial = WHOLE || tail;                                      // this workgroup leaves an fp32 partial tile
-  const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int lid = omni_xcd_contiguous(bid, nwg);
   const int band_sz = GROUP_M * tiles_n;
   const int band = lid / band_sz, in_band = lid - band * band_sz;
   const int first_m = band * GROUP_M;
@@ -1387,8 +1385,7 @@ __global__ __launch_bounds__(FIN_THREADS) void gemm_splitk_finish_kernel(const o
                                                                        int tiles_n, int GROUP_M, int nsplit) {
   const int bid = blockIdx.x / FIN_PER_TILE, quarter = blockIdx.x % FIN_PER_TILE;      // (`quarter`: the tile's 32-row slice)
   const int nwg = tiles_m * tiles_n;
-  const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int lid = omni_xcd_contiguous(bid, nwg);
   const int band_sz = GROUP_M * tiles_n;
   const int band = lid / band_sz, in_band = lid - band * band_sz;
   const int first_m = band * GROUP_M;
@@ -1415,8 +1412,7 @@ __global__ __launch_bounds__(FIN_THREADS) void gemm_tail_finish_kernel(const omn
   const int tl = blockIdx.x / FIN_PER_TILE, quarter = blockIdx.x % FIN_PER_TILE;
   const int bid = tail_first + tl;
   const int nwg = tiles_m * tiles_n;
-  const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int lid = omni_xcd_contiguous(bid, nwg);
   const int band_sz = GROUP_M * tiles_n;
   const int band = lid / band_sz, in_band = lid - band * band_sz;
   const int first_m = band * GROUP_M;

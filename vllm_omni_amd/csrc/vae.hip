@@ -20,7 +20,7 @@
 //  * omni_vae_upsample2x_bordered: nearest-exact x2 between zero-bordered rasters.
 //  * omni_softmax_rows: in-place row softmax (scale folded) for the single-head mid-block attention.
 // Roofline: conv = MFMA-bound for Cin,Cout >= 96; norm/softmax = HBM-bound.
-#include "common.h"
+#include "attention_common.h"
 
 namespace {
 
@@ -741,12 +741,6 @@ OMNI_DEVINL bf16x8_t va_read16(uint32_t addr) {                    // invisible 
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
   return v;
 }
-template <int OFF>
-OMNI_DEVINL u32x2_t va_tr_read8(uint32_t addr) {                    // ds_read_b64_tr_b16: hardware 4x4 transpose read
-  u32x2_t v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
 
 __global__ __launch_bounds__(VA_NW * 64, 1) void vae_attn_fwd_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                                     const uint16_t* __restrict__ v, uint16_t* __restrict__ out,
@@ -814,8 +808,7 @@ __global__ __launch_bounds__(VA_NW * 64, 1) void vae_attn_fwd_kernel(const uint1
   uint32_t k_addr[2];
 #pragma unroll
   for (int e = 0; e < 2; ++e) k_addr[e] = l31 * 64 + ((((uint32_t)(e * 2 + hi)) ^ ((l31 >> 2) & 3)) << 4);
-  // V (tr read): m = lane & 15, g = lane >> 4:  (m >> 2) * 64 + (g & 1) * 32 + (m & 3) * 8 + hi * 256
-  const uint32_t v_lane_off = VA_K_BYTES + ((lane & 15) >> 2) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8 + hi * 256;
+  const uint32_t v_lane_off = attn_vt_lane_addr(VA_K_BYTES, lane);
 
   f32x16_t o[12];
 #pragma unroll
@@ -868,7 +861,7 @@ __global__ __launch_bounds__(VA_NW * 64, 1) void vae_attn_fwd_kernel(const uint1
     if (kv0 + VA_KV > seq_len) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi >= seq_len) s[r] = -INFINITY;
+        if (attn_key_of(kv0, 0, r, hi) >= seq_len) s[r] = -INFINITY;
     }
     // ---- online softmax, lane-local (one cross-half exchange for the max); defer-max as in attention.hip
     bf16x8_t pf[2];
@@ -909,8 +902,8 @@ __global__ __launch_bounds__(VA_NW * 64, 1) void vae_attn_fwd_kernel(const uint1
 #define OMNI_VA_VOFF(i) (((i) % 12) * (VA_KV / 4 * 256) + ((i) / 12) * 1024)
 #define OMNI_VA_VREAD(i)                                        \
   do {                                                          \
-    vlo[(i) & 3] = va_tr_read8<OMNI_VA_VOFF(i)>(vb);            \
-    vhi[(i) & 3] = va_tr_read8<OMNI_VA_VOFF(i) + 512>(vb);      \
+    vlo[(i) & 3] = tr_read8<OMNI_VA_VOFF(i)>(vb);            \
+    vhi[(i) & 3] = tr_read8<OMNI_VA_VOFF(i) + 512>(vb);      \
   } while (0)
 #define OMNI_VA_PV(i)                                                                                            \
   do {                                                                                                           \
@@ -995,7 +988,7 @@ __global__ __launch_bounds__(THREADS) void softmax_rows_reg_kernel(uint16_t* __r
   mx = red[0];
 #pragma unroll
   for (int k = 1; k < NW; ++k) mx = fmaxf(mx, red[k]);
-  const float c2 = scale * 1.4426950408889634f;
+  const float c2 = scale * OMNI_LOG2E;
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < CH; ++i)
@@ -1037,7 +1030,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(uint16_t* __restrict_
   if (lane == 0) red[wave] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float c2 = scale * 1.4426950408889634f;
+  const float c2 = scale * OMNI_LOG2E;
   float sum = 0.f;
   for (int c = tid; c < nch; c += 256) {
     const u32x4_t w = *reinterpret_cast<const u32x4_t*>(row + c * 8);
@@ -1227,7 +1220,7 @@ extern "C" int omni_vae_attention(const omni_bf16* q, const omni_bf16* k, const 
            hipSuccess;
   }));
   hipLaunchKernelGGL(vae_attn_fwd_kernel, dim3((unsigned)((tokens + 32 * VA_NW - 1) / (32 * VA_NW)), B), dim3(VA_NW * 64), VA_LDS,
-                     static_cast<hipStream_t>(stream), q, k, v, out, ldq, ldk, ldv, ldo, tokens, scale * 1.4426950408889634f);
+                     static_cast<hipStream_t>(stream), q, k, v, out, ldq, ldk, ldv, ldo, tokens, scale * OMNI_LOG2E);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }
