@@ -51,6 +51,8 @@ const char* omni_status_string(int status);
  * ABI version, so the version cannot tell a library that reads it from one that does not: a caller that is about to set such
  * a field asks here first (and treats a library without this symbol as having no optional capability). */
 #define OMNI_FEATURE_ATTN_F16 1u /* omni_flash_attn_general reads omni_attn_params.elem_type and has fp16 kernels */
+#define OMNI_FEATURE_TEACACHE_RAGGED 2u /* omni_dit_forward's TeaCache kernels address every item by its own image-row range:
+                                         * the items of a batch with omni_dit_batch.teacache set may differ in image rows */
 uint32_t omni_features(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -565,6 +567,9 @@ typedef struct {
 typedef struct {
   /* ragged batch of n_items sequences; item i: T_i text rows then S_img image rows in the joint order */
   int32_t n_items, n_img_rows, n_txt_rows, n_joint_rows, n_temb, max_seqlen;
+  /* max_seqlen: at least the joint rows (text + image) of the longest item.  It sizes the attention grid and, with `teacache`
+   * set, the grids of the TeaCache kernels (an item's image rows never exceed its joint rows): too small a value leaves rows
+   * of the longest item unvisited without an error. */
   const omni_bf16* latents;       /* [n_img_rows, in_channels] packed latents           */
   const omni_bf16* prompt_embeds; /* [n_txt_rows, joint_dim]                            */
   const float* timestep;          /* [n_temb] sigma (the pipeline's t/1000)             */
@@ -585,7 +590,10 @@ typedef struct {
   /* workspace (caller-allocated, sizes from omni_dit_workspace_bytes) */
   void* workspace;
   size_t workspace_bytes;
-  const omni_teacache* teacache;  /* nullable: TeaCache off.  All items must have the same number of image rows.  ABI v3 */
+  const omni_teacache* teacache;  /* nullable: TeaCache off.  ABI v3.  Item i owns the image rows [img_cu[i], img_cu[i + 1]) with
+                                   * img_cu[i] = cu_seqlens[i] - teacache->txt_cu[i]: at most 64 items, each with at least one
+                                   * image row; they may differ in size in a library that reports OMNI_FEATURE_TEACACHE_RAGGED
+                                   * (one without that bit refuses unequal items with OMNI_ERR_UNSUPPORTED) */
   const omni_bf16* temb_add;      /* ABI v9, nullable: [n_temb, D] bf16 added to the timestep embedding — the Layered variant's
                                    * addition_t_embedding(additional_t_cond) rows (qwen_image_transformer.py:47-62) */
   const omni_bf16* mod_table;     /* ABI v9, nullable: [num_layers][2 (image, text stream)][n_temb][6 D] bf16 — the blocks'

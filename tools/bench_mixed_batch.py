@@ -12,6 +12,13 @@ number of DiT forwards, and next to it the device time inside the steps (the bat
 before the option existed (uniform serve states, one fused CFG + Euler launch).
 
     python tools/bench_mixed_batch.py [--layers 60] [--steps 20] [--repeats 3]
+
+With `--teacache THRESH` the DiT runs with TeaCache at that threshold and the two settings become: `mixed_step_batch` alone
+(TeaCache keeps the grid in the batch key: what serving did before `mixed_step_batch_teacache` existed) against both flags on.
+Workload B is timed, and as a control the equal-grid case C (five 1024x1024 requests), which never forms a mixed group: its
+time is the cost of the TeaCache kernels reading per-item row ranges.  `--lib PATH` loads another build of libomni_cdna4.so
+(same-box A/B of the control against the library of another commit).  Images/s and the skipped forwards per request are
+printed next to the times.
 """
 import argparse
 import os
@@ -32,6 +39,10 @@ from vllm_omni_amd.diffusion.step_batcher import ContinuousStepBatcher  # noqa: 
 WORKLOADS = {
     "A aspect-ratio mix": [(1328, 1328), (928, 1664), (1664, 928), (1056, 1584)],          # (height, width)
     "B small next to large": [(1328, 1328), (1328, 1328), (512, 512), (512, 512), (512, 512)],
+}
+TEACACHE_WORKLOADS = {
+    "B small next to large": WORKLOADS["B small next to large"],
+    "C equal grid (control)": [(1024, 1024)] * 5,
 }
 DEV = "cuda:0"
 
@@ -72,12 +83,68 @@ def run(pipe, tr, reqs):
     return dt, calls[0], busy
 
 
+def run_teacache(pipe, tr, reqs):
+    """`run`, plus the skipped forwards of every request's (positive, negative) branch, read after the loop."""
+    skipped, orig = {}, pipe._export_sample
+
+    def export(a):
+        orig(a)
+        if a.state.get("tc"):
+            skipped[a.tag] = tuple(int(x["skip_total"][0]) for x in a.state["tc"])
+
+    pipe._export_sample = export
+    try:
+        dt, calls, busy = run(pipe, tr, reqs)
+    finally:
+        del pipe._export_sample
+    return dt, calls, busy, [skipped.get(i) for i in range(len(reqs))]
+
+
+def main_teacache(a):
+    from vllm_omni_amd import _native as N
+    from vllm_omni_amd.diffusion.cache.teacache.config import TeaCacheConfig
+
+    if a.lib:
+        N.LIB_PATH = os.path.abspath(a.lib)
+    print(f"library {N.LIB_PATH}: features {N.features():#x}; TeaCache rel_l1_thresh {a.teacache}, {a.layers} layers, {a.steps} steps", flush=True)
+    tr = QwenImageTransformer2DModel(num_layers=a.layers, device=DEV).init_random_(seed=1)
+    tr.teacache = TeaCacheConfig(rel_l1_thresh=a.teacache)
+    cfgs = {"grid in key": dict(mixed_step_batch=True)}
+    if N.features() & N.FEATURE_TEACACHE_RAGGED:
+        cfgs["both flags"] = dict(mixed_step_batch=True, mixed_step_batch_teacache=True)
+    pipes = {k: QwenImagePipeline(od_config=OmniDiffusionConfig(max_step_batch=5, **c), device=DEV, transformer=tr) for k, c in cfgs.items()}
+    for name, sizes in TEACACHE_WORKLOADS.items():
+        if a.only and not name.startswith(a.only):
+            continue
+        reqs = requests(sizes, a.steps)
+        for p in pipes.values():
+            run(p, tr, requests(sizes, 2))
+        times, fwd, skips = {k: [] for k in pipes}, {}, {}
+        for _ in range(a.repeats):
+            for k, p in pipes.items():
+                dt, fwd[k], _, skips[k] = run_teacache(p, tr, reqs)
+                times[k].append(dt)
+        for k in pipes:
+            t = times[k]
+            print(f"{name} | {k}: {fwd[k]} forwards, wall s per repeat {' '.join(f'{x:.3f}' for x in t)} (median "
+                  f"{statistics.median(t):.3f}, spread {max(t) - min(t):.3f}) = {len(reqs) / statistics.median(t):.3f} images/s; "
+                  f"skipped forwards per request (pos, neg) {skips[k]}", flush=True)
+        if len(pipes) == 2:
+            print(f"{name} | both flags / grid in key (medians) = "
+                  f"{statistics.median(times['both flags']) / statistics.median(times['grid in key']):.3f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=60)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--teacache", type=float, default=None, metavar="THRESH")
+    ap.add_argument("--lib", default=None, help="another build of libomni_cdna4.so (with --teacache)")
+    ap.add_argument("--only", default=None, help="with --teacache: the workload whose name starts with this (B or C)")
     a = ap.parse_args()
+    if a.teacache is not None:
+        return main_teacache(a)
     tr = QwenImageTransformer2DModel(num_layers=a.layers, device=DEV).init_random_(seed=1)
     pipes = {"flag off": QwenImagePipeline(od_config=OmniDiffusionConfig(max_step_batch=5), device=DEV, transformer=tr),
              "flag on": QwenImagePipeline(od_config=OmniDiffusionConfig(max_step_batch=5, mixed_step_batch=True), device=DEV,

@@ -226,6 +226,7 @@ PROTOTYPES = {
 # padding, which keeps the version.  `features()` is how callers ask.
 OPTIONAL_SYMBOLS = ("omni_features",)
 FEATURE_ATTN_F16 = 1                              # OMNI_FEATURE_ATTN_F16
+FEATURE_TEACACHE_RAGGED = 2                       # OMNI_FEATURE_TEACACHE_RAGGED
 ELEM_BF16, ELEM_F16 = 0, 1                        # omni_attn_params.elem_type
 
 _lib = None

@@ -187,10 +187,12 @@ int omni_internal_flash_attn(const omni_bf16* q, const omni_bf16* k, const omni_
 // q_prescaled = 1 for a q that already carries softmax_scale * log2(e); workspace / alignment checked here, the rest by the caller
 int omni_internal_sage_attn(const omni_attn_params* p, const int32_t* item_skip, int32_t q_prescaled, void* stream);
 // internal: TeaCache device-side decision / residual kernels (elementwise.hip), used by omni_dit_forward
-int omni_internal_teacache_decide(const omni_teacache* tc, const omni_bf16* mod, int32_t n_items, int32_t rows_per_item,
-                                  int32_t n_img_rows, int32_t n_txt_rows, int32_t D, int32_t blocked, void* stream);
-int omni_internal_teacache_post(const omni_teacache* tc, omni_bf16* hidden, const omni_bf16* hidden_in, int32_t n_img_rows,
-                                int32_t rows_per_item, int32_t D, void* stream);
+int omni_internal_teacache_decide(const omni_teacache* tc, const omni_bf16* mod, const int32_t* cu_seqlens, int32_t n_items,
+                                  int32_t max_item_rows, int32_t n_img_rows, int32_t n_txt_rows, int32_t D, int32_t blocked,
+                                  void* stream);
+int omni_internal_teacache_post(const omni_teacache* tc, omni_bf16* hidden, const omni_bf16* hidden_in,
+                                const int32_t* cu_seqlens, int32_t n_items, int32_t max_item_rows, int32_t n_img_rows,
+                                int32_t D, void* stream);
 // Tuning knobs: the product library reads NOTHING from the process environment and keeps no mutable global state; a build with
 // -DOMNI_DEV (tools/build_variants.sh: same-box A/B runs) reads its knobs through this one function.
 #ifdef OMNI_DEV

@@ -482,9 +482,11 @@ extern "C" int omni_dit_forward(const omni_dit_weights* w, const omni_dit_batch*
 
   OMNI_TRY(prepare_positions(b, ws, stream));
   const omni_teacache* tc = b->teacache;
-  const int32_t rows_per_item = b->n_items > 0 ? Ri / b->n_items : 0;
+  // the items address their image rows through cu_seqlens - txt_cu on the device (OMNI_FEATURE_TEACACHE_RAGGED); the host has
+  // no per-item lengths here, only a bound of the largest: an item's joint rows (text + image) are at most max_seqlen
+  const int32_t tc_max_rows = b->max_seqlen < Ri ? b->max_seqlen : Ri;
   if (tc) {
-    if (rows_per_item * b->n_items != Ri || b->n_items > 64) return OMNI_ERR_UNSUPPORTED;
+    if (b->n_items <= 0 || b->n_items > 64 || Ri < b->n_items || !b->cu_seqlens || tc_max_rows <= 0) return OMNI_ERR_UNSUPPORTED;
     // the image stream as it enters the block stack: residual = out - this; skipped items leave as this + cached residual
     if (hipMemcpyAsync(ws.h_in, ws.hidden_img, (size_t)Ri * D * sizeof(omni_bf16), hipMemcpyDeviceToDevice,
                        static_cast<hipStream_t>(stream)) != hipSuccess)
@@ -499,7 +501,7 @@ extern "C" int omni_dit_forward(const omni_dit_weights* w, const omni_dit_batch*
       // decision on the first block's modulated input, BEFORE anything of the block stack that could be skipped; the
       // predicates it writes gate every GEMM row tile / attention block of skipped items from here on
       auto hook = [&](omni_bf16* xn_img) {
-        return omni_internal_teacache_decide(tc, xn_img, b->n_items, rows_per_item, Ri, Rt, D, blocked, stream);
+        return omni_internal_teacache_decide(tc, xn_img, b->cu_seqlens, b->n_items, tc_max_rows, Ri, Rt, D, blocked, stream);
       };
       OMNI_TRY(run_block(w, l, b, ws, ws.hidden_img, ws.hidden_txt, ws.temb, pred, hook, stream, BLOCK_ALL, nullptr, &pend, more));
     } else {
@@ -507,7 +509,7 @@ extern "C" int omni_dit_forward(const omni_dit_weights* w, const omni_dit_batch*
     }
   }
   if (pend.nsplit > 1) return OMNI_ERR_LAUNCH;          // (cannot happen: the last block never defers)
-  if (tc) OMNI_TRY(omni_internal_teacache_post(tc, ws.hidden_img, ws.h_in, Ri, rows_per_item, D, stream));
+  if (tc) OMNI_TRY(omni_internal_teacache_post(tc, ws.hidden_img, ws.h_in, b->cu_seqlens, b->n_items, tc_max_rows, Ri, D, stream));
 
   omni_bf16* xn_img = ws.xn;
   // --- output head: AdaLayerNormContinuous (scale first, then shift) + proj_out (reference :797-798) -------

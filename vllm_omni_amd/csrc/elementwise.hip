@@ -654,17 +654,37 @@ int omni_internal_gather_i32(int32_t* dst, const int32_t* src, const int32_t* id
 // TeaCache on the device (reference vllm_omni/diffusion/cache/teacache/hook.py:170-217; see omni_teacache in the header).
 // ------------------------------------------------------------------------------------------------
 namespace {
-// Partial sums of |mod - prev| and |prev| per item, and prev <- mod, in one pass.  The buffer is NSEG x n_items segments of
-// `seg_elems` contiguous elements: (NSEG, W) = (D/32, 32) for the K32-blocked layout [D/32][rows][32], (1, D) for row-major.
-// grid = (blocks per segment, n_items, NSEG)
+// Items address their image rows through their OWN row range (OMNI_FEATURE_TEACACHE_RAGGED): item i owns the image rows
+// [img_cu[i], img_cu[i + 1]) with img_cu[i] = cu_seqlens[i] - txt_cu[i] (joint prefix sums minus text prefix sums, both already
+// on the device), so the items of a forward may sit on different token grids.  A range that is empty or leaves the buffer
+// (a descriptor the host could not check) is never dereferenced.
+__device__ __forceinline__ bool teacache_item_rows(const int32_t* __restrict__ cu, const int32_t* __restrict__ txt_cu, int item,
+                                                   int n_img_rows, int& r0, int& r1) {
+  r0 = cu[item] - txt_cu[item];
+  r1 = cu[item + 1] - txt_cu[item + 1];
+  return r0 >= 0 && r1 > r0 && r1 <= n_img_rows;
+}
+
+// Partial sums of |mod - prev| and |prev| per item, and prev <- mod, in one pass.  The buffer is NSEG slabs of n_img_rows x W
+// elements: (NSEG, W) = (D/32, 32) for the K32-blocked layout [D/32][rows][32], (1, D) for row-major; the item's segment of
+// slab z starts at (z * n_img_rows + img_cu[item]) * W and holds rows_i * W contiguous elements.
+// grid = (blocks per segment of the LARGEST item, n_items, NSEG).  An item's sums must not depend on who shares the forward: the
+// number of workgroups that work on item i, and with it the grid stride, comes from the item's own size (min(64, ceil(rows_i * W
+// / 8 / 256)), the launch's formula for a batch of equal items); the surplus workgroups of a smaller item return.  Every thread's
+// partial sums are therefore those of the item's solo run; only the order of the atomic adds differs, as it does between any
+// two runs.
 __global__ __launch_bounds__(256) void teacache_reduce_kernel(const uint16_t* __restrict__ mod, uint16_t* __restrict__ prev,
-                                                              float* __restrict__ scratch, int64_t seg_stride_item,
-                                                              int64_t seg_stride_slab, int64_t seg_elems) {
+                                                              float* __restrict__ scratch, const int32_t* __restrict__ cu,
+                                                              const int32_t* __restrict__ txt_cu, int n_img_rows, int W) {
   const int item = blockIdx.y;
-  const int64_t base = (int64_t)blockIdx.z * seg_stride_slab + (int64_t)item * seg_stride_item;
-  const int64_t nchunk = seg_elems / 8;
+  int r0, r1;
+  if (!teacache_item_rows(cu, txt_cu, item, n_img_rows, r0, r1)) return;
+  const int64_t nchunk = (int64_t)(r1 - r0) * W / 8;
+  const int nblk = (int)min((int64_t)64, (nchunk + 255) / 256);
+  if ((int)blockIdx.x >= nblk) return;
+  const int64_t base = ((int64_t)blockIdx.z * n_img_rows + r0) * W;
   float sd = 0.f, sp = 0.f;
-  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (int64_t)nblk * blockDim.x) {
     const u32x4_t m = *reinterpret_cast<const u32x4_t*>(mod + base + c * 8);
     const u32x4_t p = *reinterpret_cast<const u32x4_t*>(prev + base + c * 8);
 #pragma unroll
@@ -689,19 +709,24 @@ __global__ __launch_bounds__(256) void teacache_reduce_kernel(const uint16_t* __
 }
 
 // one workgroup: per-item decision, statistics, and the per-row-tile predicates of both streams
-__global__ __launch_bounds__(256) void teacache_decide_kernel(omni_teacache tc, int n_items, int rows_per_item,
-                                                              int n_img_rows, int n_txt_rows, float inv_count) {
+__global__ __launch_bounds__(256) void teacache_decide_kernel(omni_teacache tc, const int32_t* __restrict__ cu, int n_items,
+                                                              int n_img_rows, int n_txt_rows, int D) {
   __shared__ int s_skip[64];
+  __shared__ int s_img_cu[65];
   const int i = threadIdx.x;
+  if (i <= n_items) s_img_cu[i] = cu[i] - tc.txt_cu[i];
   if (i < n_items) {
     int skip = 0;
     const int cnt = tc.cnt[i];
     float acc = tc.acc_dist[i];
-    if (cnt == 0) {
-      acc = 0.f;                                           // first forward of a generation: always compute (:185-188)
+    int r0, r1;
+    if (cnt == 0 || !teacache_item_rows(cu, tc.txt_cu, i, n_img_rows, r0, r1)) {
+      acc = 0.f;                 // first forward of a generation: always compute (:185-188); so does an item whose row range
+                                 // is not one (a descriptor the host could not check): the reduce left its sums untouched
     } else {
       // the reference forms this ratio from bf16 tensors: .abs().mean() -> bf16, (+ 1e-8) -> bf16, division -> bf16
       auto rb = [](float x) { return bf16_bits_to_f32(f32_to_bf16_bits(x)); };
+      const float inv_count = 1.0f / ((float)(r1 - r0) * (float)D);      // the mean runs over the item's own rows_i * D elements
       const float rel = rb(rb(tc.scratch[2 * i] * inv_count) / rb(rb(tc.scratch[2 * i + 1] * inv_count) + 1e-8f));
       float r = tc.coeff[0];
 #pragma unroll
@@ -719,10 +744,12 @@ __global__ __launch_bounds__(256) void teacache_decide_kernel(omni_teacache tc, 
     s_skip[i] = skip;
   }
   __syncthreads();
+  // a row tile is skipped when EVERY item with a row in it is (a tile may straddle items of different sizes)
   for (int t = threadIdx.x; t < (n_img_rows + 255) / 256; t += blockDim.x) {
-    const int first = (t * 256) / rows_per_item, last = min(t * 256 + 255, n_img_rows - 1) / rows_per_item;
+    const int r0 = t * 256, r1 = min(t * 256 + 255, n_img_rows - 1);
     int all = 1;
-    for (int it = first; it <= last; ++it) all &= s_skip[it];
+    for (int it = 0; it < n_items; ++it)
+      if (s_img_cu[it] <= r1 && s_img_cu[it + 1] > r0) all &= s_skip[it];
     tc.tile_skip_img[t] = all;
   }
   for (int t = threadIdx.x; t < (n_txt_rows + 255) / 256; t += blockDim.x) {
@@ -734,15 +761,22 @@ __global__ __launch_bounds__(256) void teacache_decide_kernel(omni_teacache tc, 
   }
 }
 
-// after the block stack: skipped items take hidden_in + cached residual; computed items refresh the residual
+// after the block stack: skipped items take hidden_in + cached residual; computed items refresh the residual.
+// grid = (blocks per item, n_items): a workgroup works on ONE item's chunks, so the decision is uniform in it
 __global__ __launch_bounds__(256) void teacache_post_kernel(uint16_t* __restrict__ hidden, const uint16_t* __restrict__ hin,
                                                             uint16_t* __restrict__ res, const int32_t* __restrict__ skip,
-                                                            int64_t nchunk, int chunks_per_item) {
-  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (int64_t)gridDim.x * blockDim.x) {
-    const int item = (int)(c / chunks_per_item);
+                                                            const int32_t* __restrict__ cu, const int32_t* __restrict__ txt_cu,
+                                                            int n_img_rows, int chunks_per_row) {
+  const int item = blockIdx.y;
+  int r0, r1;
+  if (!teacache_item_rows(cu, txt_cu, item, n_img_rows, r0, r1)) return;
+  const int64_t c1 = (int64_t)r1 * chunks_per_row;
+  const bool skipped = skip[item] != 0;
+  for (int64_t c = (int64_t)r0 * chunks_per_row + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < c1;
+       c += (int64_t)gridDim.x * blockDim.x) {
     const u32x4_t a = *reinterpret_cast<const u32x4_t*>(hin + c * 8);
     u32x4_t o;
-    if (skip[item]) {
+    if (skipped) {
       const u32x4_t r = *reinterpret_cast<const u32x4_t*>(res + c * 8);
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(bf16_lo(a[e]) + bf16_lo(r[e]), bf16_hi(a[e]) + bf16_hi(r[e]));
@@ -803,33 +837,40 @@ __global__ __launch_bounds__(256) void quantize_fp8_rows_kernel(const uint16_t* 
 }
 }  // namespace
 
-int omni_internal_teacache_decide(const omni_teacache* tc, const omni_bf16* mod, int32_t n_items, int32_t rows_per_item,
-                                  int32_t n_img_rows, int32_t n_txt_rows, int32_t D, int32_t blocked, void* stream) {
-  if (!tc || !mod || !tc->prev_mod || !tc->prev_res || !tc->acc_dist || !tc->cnt || !tc->skip || !tc->skip_total ||
-      !tc->scratch || !tc->tile_skip_img || !tc->tile_skip_txt || !tc->txt_cu)
+// `cu_seqlens` / tc->txt_cu: DEVICE prefix sums (omni_dit_batch / omni_teacache); `max_item_rows`: a host-side bound of the
+// largest item's image rows (it only sizes the grids: an item's own size decides what its workgroups do).
+int omni_internal_teacache_decide(const omni_teacache* tc, const omni_bf16* mod, const int32_t* cu_seqlens, int32_t n_items,
+                                  int32_t max_item_rows, int32_t n_img_rows, int32_t n_txt_rows, int32_t D, int32_t blocked,
+                                  void* stream) {
+  if (!tc || !mod || !cu_seqlens || !tc->prev_mod || !tc->prev_res || !tc->acc_dist || !tc->cnt || !tc->skip ||
+      !tc->skip_total || !tc->scratch || !tc->tile_skip_img || !tc->tile_skip_txt || !tc->txt_cu)
     return OMNI_ERR_BAD_ARG;
-  if (n_items <= 0 || n_items > 64 || rows_per_item <= 0 || n_items * rows_per_item != n_img_rows || D % 32)
-    return OMNI_ERR_UNSUPPORTED;
+  // every item needs at least one image row: more items than rows cannot be a valid batch
+  if (n_items <= 0 || n_items > 64 || n_img_rows < n_items || max_item_rows <= 0 || D % 32) return OMNI_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nseg = blocked ? D / 32 : 1, W = blocked ? 32 : D;
-  const int64_t seg_elems = (int64_t)rows_per_item * W;
+  const int64_t seg_elems = (int64_t)(max_item_rows < n_img_rows ? max_item_rows : n_img_rows) * W;
   int bx = (int)((seg_elems / 8 + 255) / 256);
   if (bx > 64) bx = 64;
   hipLaunchKernelGGL(teacache_reduce_kernel, dim3(bx, n_items, nseg), dim3(256), 0, s, mod, tc->prev_mod, tc->scratch,
-                     seg_elems, (int64_t)n_img_rows * W, seg_elems);
+                     cu_seqlens, tc->txt_cu, n_img_rows, W);
   OMNI_CHECK_LAUNCH();
-  hipLaunchKernelGGL(teacache_decide_kernel, dim3(1), dim3(256), 0, s, *tc, n_items, rows_per_item, n_img_rows, n_txt_rows,
-                     1.0f / ((float)rows_per_item * (float)D));
+  hipLaunchKernelGGL(teacache_decide_kernel, dim3(1), dim3(256), 0, s, *tc, cu_seqlens, n_items, n_img_rows, n_txt_rows, D);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }
 
-int omni_internal_teacache_post(const omni_teacache* tc, omni_bf16* hidden, const omni_bf16* hidden_in, int32_t n_img_rows,
-                                int32_t rows_per_item, int32_t D, void* stream) {
-  if (!tc || !hidden || !hidden_in) return OMNI_ERR_BAD_ARG;
-  const int64_t nchunk = (int64_t)n_img_rows * D / 8;
-  hipLaunchKernelGGL(teacache_post_kernel, dim3(2048), dim3(256), 0, static_cast<hipStream_t>(stream), hidden, hidden_in,
-                     tc->prev_res, tc->skip, nchunk, rows_per_item * (D / 8));
+int omni_internal_teacache_post(const omni_teacache* tc, omni_bf16* hidden, const omni_bf16* hidden_in,
+                                const int32_t* cu_seqlens, int32_t n_items, int32_t max_item_rows, int32_t n_img_rows,
+                                int32_t D, void* stream) {
+  if (!tc || !hidden || !hidden_in || !cu_seqlens || !tc->txt_cu || !tc->skip || !tc->prev_res) return OMNI_ERR_BAD_ARG;
+  if (n_items <= 0 || n_items > 64 || n_img_rows < n_items || max_item_rows <= 0 || D % 8) return OMNI_ERR_UNSUPPORTED;
+  // about 2048 workgroups in all, as the launch over the whole buffer had; never more than the largest item has chunks for
+  const int64_t item_chunks = (int64_t)(max_item_rows < n_img_rows ? max_item_rows : n_img_rows) * (D / 8);
+  int64_t bx = (2048 + n_items - 1) / n_items;
+  if (bx > (item_chunks + 255) / 256) bx = (item_chunks + 255) / 256;
+  hipLaunchKernelGGL(teacache_post_kernel, dim3((unsigned)bx, n_items), dim3(256), 0, static_cast<hipStream_t>(stream), hidden,
+                     hidden_in, tc->prev_res, tc->skip, cu_seqlens, tc->txt_cu, n_img_rows, D / 8);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }

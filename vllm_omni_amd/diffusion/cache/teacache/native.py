@@ -22,6 +22,17 @@ class TeaCacheDeviceState:
         if n > 64:
             raise ValueError("TeaCache device state supports at most 64 items per step-batch")
         self.n_items, self.rows = n, (Ri, Rt)
+        # item i owns the image rows [img_off[i], img_off[i + 1]) of both history buffers (the kernels form the same prefix sums
+        # on the device: cu_seqlens - txt_cu)
+        if any(int(s) < 1 for s in rb.s_imgs):
+            raise ValueError("TeaCache device state: every item needs at least one image row")
+        self.img_off = [0]
+        for s in rb.s_imgs:
+            self.img_off.append(self.img_off[-1] + int(s))
+        if len(set(rb.s_imgs)) > 1 and not N.features() & N.FEATURE_TEACACHE_RAGGED:
+            raise N.OmniNativeError("this libomni_cdna4.so does not report OMNI_FEATURE_TEACACHE_RAGGED: its TeaCache kernels "
+                                    "address an item's image rows as item * rows_per_item and cannot take items of "
+                                    f"{sorted(set(rb.s_imgs))} image rows in one forward")
         self.prev_mod = torch.zeros(Ri * D, dtype=BF16, device=device)
         self.prev_res = torch.zeros(Ri * D, dtype=BF16, device=device)
         self.acc = torch.zeros(n, dtype=torch.float32, device=device)
@@ -49,10 +60,10 @@ class TeaCacheDeviceState:
     # is re-composed).  prev_mod has the layout the first AdaLN writes: K32-blocked [D/32][rows][32] when D % 32 == 0.
     def _item_views(self, i: int):
         Ri = self.rows[0]
-        S = Ri // self.n_items
+        o0, o1 = self.img_off[i], self.img_off[i + 1]
         D = self.prev_res.numel() // Ri
-        res = self.prev_res.view(Ri, D)[i * S:(i + 1) * S]
-        mod = self.prev_mod.view(D // 32, Ri, 32)[:, i * S:(i + 1) * S] if D % 32 == 0 else self.prev_mod.view(Ri, D)[i * S:(i + 1) * S]
+        res = self.prev_res.view(Ri, D)[o0:o1]
+        mod = self.prev_mod.view(D // 32, Ri, 32)[:, o0:o1] if D % 32 == 0 else self.prev_mod.view(Ri, D)[o0:o1]
         return mod, res
 
     def export_item(self, i: int) -> dict:
@@ -74,7 +85,7 @@ class TeaCacheDeviceState:
         self.skip_total[i:i + 1].copy_(saved["skip_total"])
 
     def struct_for(self, rb: RaggedBatch) -> N.TeaCache:
-        if (rb.n_img_rows, rb.n_txt_rows) != self.rows or rb.n_items != self.n_items:
+        if (rb.n_img_rows, rb.n_txt_rows) != self.rows or rb.n_items != self.n_items or rb.img_offsets != self.img_off:
             raise ValueError("TeaCache state was built for a different batch")
         return self._struct
 

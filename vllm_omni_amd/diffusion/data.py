@@ -134,6 +134,9 @@ class OmniDiffusionConfig:
     mixed_step_batch: bool = False   # NEW, opt-in: text-to-image requests of DIFFERENT resolutions and true-CFG scales share a
                                      # DiT forward (the batch key drops the grid and the scale).  Off: every batch
                                      # key and every code path is what it was
+    mixed_step_batch_teacache: bool = False  # NEW, opt-in, only together with mixed_step_batch: mixed groups also form when
+                                     # TeaCache is configured (its kernels address every item by its own image-row range,
+                                     # OMNI_FEATURE_TEACACHE_RAGGED).  Off: TeaCache keeps the grid in the batch key
     max_step_tokens: int | None = None  # NEW: admission bound next to max_step_batch — the largest sum of image rows x CFG
                                      # branches one forward may hold (the oldest sample always runs, alone if need be)
     # ---- the reference's remaining fields (data.py:255-360), so that a config written for it constructs here unchanged.
@@ -200,6 +203,9 @@ class OmniDiffusionConfig:
                 logger.warning("Unknown dtype string '%s', defaulting to bfloat16", self.dtype)
                 known = torch.bfloat16
             self.dtype = known
+        if self.mixed_step_batch_teacache and not self.mixed_step_batch:
+            raise ValueError("mixed_step_batch_teacache=True extends mixed_step_batch and means nothing without it: set "
+                             "mixed_step_batch=True as well")
         if self.cache_backend is None:
             self.cache_backend = "none"
         if self.cache_backend not in ("none", "tea_cache", "teacache"):

@@ -548,15 +548,20 @@ class QwenImagePipeline(nn.Module):
         """What one ragged forward can mix.  Default: one token grid and one true-CFG scale per forward.  With
         `od_config.mixed_step_batch` plain text-to-image samples of ANY grid and scale share a key (the kernels address rows
         through per-item maps; the CFG + Euler update runs per request).  The grid stays in the key for samples that carry
-        condition rows (Edit / Edit-Plus / Layered: multi-entry grids) and whenever TeaCache is configured (its reductions
-        assume equal image rows per item)."""
+        condition rows (Edit / Edit-Plus / Layered: multi-entry grids) and, unless `od_config.mixed_step_batch_teacache` is
+        set as well, whenever TeaCache is configured."""
         sm = a.sample
-        if getattr(self.od_config, "mixed_step_batch", False) and sm.get("cond") is None and not self._teacache_configured():
+        if (getattr(self.od_config, "mixed_step_batch", False) and sm.get("cond") is None
+                and (self._mixed_teacache() or not self._teacache_configured())):
             return ("mixed", sm["do_cfg"], sm.get("cfg_normalize", True), sm.get("t_cond"))
         return (sm["grid"], sm["do_cfg"], sm["cfg"], sm.get("cfg_normalize", True), sm.get("t_cond"))
 
     def _teacache_configured(self) -> bool:
         return self.cache_backend is not None or getattr(self.transformer, "teacache", None) is not None
+
+    def _mixed_teacache(self) -> bool:
+        """May a mixed group run with TeaCache?  (Both opt-ins: the TeaCache kernels then take items of unequal image rows.)"""
+        return bool(getattr(self.od_config, "mixed_step_batch", False) and getattr(self.od_config, "mixed_step_batch_teacache", False))
 
     # A "serve state" = everything one composition of a running batch needs, allocated ONCE: the static input / output
     # buffers of the forward, the ragged-batch descriptor, the per-request timestep / dt vectors, the TeaCache device state
@@ -583,7 +588,7 @@ class QwenImagePipeline(nn.Module):
             if any(a.state.get("cond") is not None for a in group):
                 raise NotImplementedError("a mixed step-batch cannot hold samples with condition-image rows (Edit / Edit-Plus / "
                                           "Layered): their multi-entry grids must be the same for every item of a forward")
-            if tcfg is not None:
+            if tcfg is not None and not self._mixed_teacache():
                 raise NotImplementedError("a mixed step-batch cannot run with TeaCache: its residual reductions assume the same "
                                           "number of image rows for every item (omni_teacache)")
         S_list = [int(a.state["lat"].shape[0]) for a in group]
@@ -592,6 +597,8 @@ class QwenImagePipeline(nn.Module):
             img_off.append(img_off[-1] + s_)                  # slot r's latent rows: [img_off[r], img_off[r + 1]); r * S when equal
         if mixed:      # the key names the ordered sizes and scales (the batcher orders a group longest first: canonical)
             key = ("mixed", tuple(lens), tuple(grids), do_cfg, tuple(cfgs), R, sm0.get("cfg_normalize", True), sm0.get("t_cond"), use_tab)
+            if tcfg is not None:                              # (only with mixed_step_batch_teacache: the key is what it was without)
+                key += ((tcfg.rel_l1_thresh, tuple(tcfg.coefficients)),)
         else:
             key = (tuple(lens), tuple(sm0["grid"]), do_cfg, float(sm0["cfg"]), R, S_c, sm0.get("cfg_normalize", True), sm0.get("t_cond"),
                    use_tab, None if tcfg is None else (tcfg.rel_l1_thresh, tuple(tcfg.coefficients)))
