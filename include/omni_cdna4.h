@@ -53,6 +53,7 @@ const char* omni_status_string(int status);
 #define OMNI_FEATURE_ATTN_F16 1u /* omni_flash_attn_general reads omni_attn_params.elem_type and has fp16 kernels */
 #define OMNI_FEATURE_TEACACHE_RAGGED 2u /* omni_dit_forward's TeaCache kernels address every item by its own image-row range:
                                          * the items of a batch with omni_dit_batch.teacache set may differ in image rows */
+#define OMNI_FEATURE_CFG_EULER_RAGGED 4u /* the library exports omni_cfg_euler_step_ragged: a function pointer, see there */
 uint32_t omni_features(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -429,6 +430,34 @@ int omni_cfg_euler_step(const omni_bf16* pos, const omni_bf16* neg, omni_bf16* l
 int omni_cfg_euler_step_ex(const omni_bf16* pos, const omni_bf16* neg, omni_bf16* latents, int32_t rows, int32_t C,
                            float true_cfg_scale, const float* dt, int32_t dt_rows_per_item, int32_t normalize,
                            omni_stream stream);
+
+/* The same update for R <= 64 requests of DIFFERENT row counts in ONE launch, reading the predictions where a ragged forward
+ * wrote them and writing the new rows into the forward's input buffer as well (optional symbol of ABI v14: ask
+ * omni_features() & OMNI_FEATURE_CFG_EULER_RAGGED).  Request r is described by reqs[r], an array in DEVICE memory:
+ *   lat_row            first of its `rows` rows in `latents`  [n_lat_rows, C]   (updated in place)
+ *   pos_row, neg_row   first row of its positive / negative prediction in `pred` [n_pred_rows, C]: the request's first `rows`
+ *                      rows of an item that may hold further (condition-image) rows behind them; neg_row < 0: no CFG
+ *   dst_row[0..1]      first rows in `lat_in` [n_in_rows, C] that receive a copy of the updated rows (the next forward's input
+ *                      rows of the positive and the negative item); < 0: none.  No other row of `lat_in` is touched
+ *   dt_index           its entry of the DEVICE fp32 array dt[n_dt];  cfg_scale: its true-CFG scale
+ * Arithmetic per row: omni_cfg_euler_step_ex's, bit for bit.  total_rows = the sum of reqs[r].rows (sizes the launch: rows
+ * behind it are not updated; a larger value is harmless).  The row ranges of different requests must not overlap.  The device
+ * descriptors cannot be validated by the host: the kernel skips a request whose ranges leave [0, n_*_rows) or [0, n_dt), so
+ * nothing outside the three buffers is read or written.  C == 64 and R <= 64, else OMNI_ERR_UNSUPPORTED; pred / latents /
+ * lat_in 16-byte aligned, reqs / dt 4-byte aligned, else OMNI_ERR_ALIGN. */
+typedef struct omni_cfg_euler_req {
+  int32_t lat_row, rows, pos_row, neg_row;
+  int32_t dst_row[2];
+  int32_t dt_index;
+  float cfg_scale;
+} omni_cfg_euler_req; /* 32 bytes */
+/* Exported as a const function POINTER, not as a function: the set of exported functions identifies ABI v14 and stays what
+ * it was, so an entry point added within the version is a data symbol.  C callers call it with the syntax of
+ * a function call; a dlsym / ctypes caller reads the pointer and calls its target. */
+extern int (*const omni_cfg_euler_step_ragged)(const omni_bf16* pred, int32_t n_pred_rows, omni_bf16* latents,
+                                               int32_t n_lat_rows, omni_bf16* lat_in, int32_t n_in_rows,
+                                               const omni_cfg_euler_req* reqs, int32_t R, int32_t total_rows, int32_t C,
+                                               const float* dt, int32_t n_dt, int32_t normalize, omni_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * VAE kernels (AutoencoderKLQwenImage.decode — and .encode for the Edit pipelines — for one frame,

@@ -19,6 +19,13 @@ Workload B is timed, and as a control the equal-grid case C (five 1024x1024 requ
 time is the cost of the TeaCache kernels reading per-item row ranges.  `--lib PATH` loads another build of libomni_cdna4.so
 (same-box A/B of the control against the library of another commit).  Images/s and the skipped forwards per request are
 printed next to the times.
+
+With `--edit` the workload is Edit traffic: three Edit requests near 1024^2 with different aspect ratios (1024x1024, 1376x768,
+896x1184; each carries the condition rows of a picture of its own size), true-CFG with different scales.  Settings:
+`mixed_step_batch` alone (a sample with condition rows keeps its grid in the key: one request per forward, what serving did
+before `mixed_step_batch_edit`), run TWICE per repeat to state the spread of that box, against both flags on.  Then the step
+update alone: one launch of the ragged CFG + Euler kernel against the R per-request launches and the 2R + 1 copies it
+replaces, on the same buffers (HIP events around 200 iterations).
 """
 import argparse
 import os
@@ -134,8 +141,102 @@ def main_teacache(a):
                   f"{statistics.median(times['both flags']) / statistics.median(times['grid in key']):.3f}", flush=True)
 
 
+EDIT_SIZES = [(1024, 1024, 4.0), (768, 1376, 2.5), (1184, 896, 3.0)]            # (height, width, true_cfg_scale)
+
+
+def edit_requests(steps):
+    g = torch.Generator(device=DEV).manual_seed(1)
+    rnd = lambda *s: torch.randn(*s, device=DEV, generator=g).bfloat16()  # noqa: E731
+    out = []
+    for i, (h, w, cfg) in enumerate(EDIT_SIZES):
+        S = (h // 16) * (w // 16)
+        out.append(OmniDiffusionRequest(height=h, width=w, num_inference_steps=steps, true_cfg_scale=cfg, latents=rnd(1, S, 64),
+                                        prompt_embeds=rnd(1, 200 + 17 * i, 3584), negative_prompt_embeds=rnd(1, 180 + 5 * i, 3584),
+                                        output_type="latent",
+                                        extra={"image_latents": rnd(S, 64), "image_latent_grid": (h // 16, w // 16)}))
+    return out
+
+
+def time_step_update(iters=200):
+    """One ragged launch against what it replaces, for the three Edit requests as a CFG pair group."""
+    from vllm_omni_amd import ops
+    from vllm_omni_amd.diffusion.batch import ragged_step_descriptors
+
+    S = [(h // 16) * (w // 16) for h, w, _ in EDIT_SIZES]
+    R, scales = len(S), [c for _, _, c in EDIT_SIZES]
+    lay = ragged_step_descriptors(S, S, True, scales)
+    lo, io, n_lat = lay["lat_off"], lay["item_off"], lay["total_rows"]
+    g = torch.Generator(device=DEV).manual_seed(2)
+    rnd = lambda *s: torch.randn(*s, device=DEV, generator=g).bfloat16()  # noqa: E731
+    lat, pred, lat_in = rnd(n_lat, 64), rnd(io[-1], 64), rnd(io[-1], 64)
+    pred_c = torch.empty(2 * n_lat, 64, dtype=torch.bfloat16, device=DEV)
+    dt = torch.full((R,), -1e-4, device=DEV)
+    reqs = torch.from_numpy(lay["reqs"].view("<i4").reshape(R, 8).copy()).to(DEV)
+
+    def ragged():
+        ops.cfg_euler_step_ragged_(lat, pred, lat_in, reqs, R, n_lat, dt)
+
+    def replaced():                                          # 2R copies lat -> lat_in, 2R copies pred -> pred_c, R launches
+        for r in range(R):
+            for i in (r, R + r):
+                lat_in[io[i]:io[i] + S[r]].copy_(lat[lo[r]:lo[r + 1]])
+                pred_c[(i // R) * n_lat + lo[r]:(i // R) * n_lat + lo[r + 1]].copy_(pred[io[i]:io[i] + S[r]])
+        for r in range(R):
+            ops.cfg_euler_step_(lat[lo[r]:lo[r + 1]], pred_c[lo[r]:lo[r + 1]], pred_c[n_lat + lo[r]:n_lat + lo[r + 1]], scales[r],
+                                dt[r:r + 1], dt_rows_per_item=0)
+
+    out = {}
+    for name, fn in (("ragged kernel, 1 launch", ragged), (f"replaced: {4 * R} copies + {R} launches", replaced)):
+        for _ in range(10):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        rep = []
+        for _ in range(3):
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            rep.append(e0.elapsed_time(e1) * 1e3 / iters)
+        out[name] = rep
+        print(f"step update of {S} rows + as many condition rows, CFG pairs | {name}: us per step "
+              f"{' '.join(f'{x:.1f}' for x in rep)}", flush=True)
+    return out
+
+
+def main_edit(a):
+    from vllm_omni_amd.diffusion.models.qwen_image.autoencoder_kl_qwenimage import AutoencoderKLQwenImage
+    from vllm_omni_amd.diffusion.models.qwen_image.pipeline_qwen_image_edit import QwenImageEditPipeline
+
+    print(f"Edit workload {EDIT_SIZES}: {a.layers} layers, {a.steps} steps, true-CFG", flush=True)
+    tr = QwenImageTransformer2DModel(num_layers=a.layers, device=DEV).init_random_(seed=1)
+    vae = AutoencoderKLQwenImage(device=DEV, with_encoder=True)
+    mk = lambda **c: QwenImageEditPipeline(od_config=OmniDiffusionConfig(max_step_batch=5, mixed_step_batch=True, **c),  # noqa: E731
+                                           device=DEV, transformer=tr, vae=vae)
+    pipes = {"flag off": mk(), "flag off again": mk(), "flag on": mk(mixed_step_batch_edit=True)}
+    for p in pipes.values():
+        run(p, tr, edit_requests(2))
+    reqs = edit_requests(a.steps)
+    times, busy, fwd = {k: [] for k in pipes}, {k: [] for k in pipes}, {}
+    for _ in range(a.repeats):
+        for k, p in pipes.items():
+            dt, fwd[k], bs = run(p, tr, reqs)
+            times[k].append(dt)
+            busy[k].append(bs)
+    for k in pipes:
+        t = times[k]
+        print(f"Edit x3 | {k}: {fwd[k]} forwards, wall s per repeat {' '.join(f'{x:.3f}' for x in t)} (median "
+              f"{statistics.median(t):.3f}, spread {max(t) - min(t):.3f}) = {statistics.median(t) / a.steps * 1e3:.1f} ms per step of "
+              f"three requests; device s inside steps {' '.join(f'{x:.3f}' for x in busy[k])}", flush=True)
+    off = statistics.median(times["flag off"] + times["flag off again"])
+    print(f"Edit x3 | flag on / flag off (medians) = {statistics.median(times['flag on']) / off:.3f}; flag off again / flag off = "
+          f"{statistics.median(times['flag off again']) / statistics.median(times['flag off']):.3f}", flush=True)
+    time_step_update()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--edit", action="store_true", help="Edit traffic: mixed_step_batch_edit against one request per forward")
     ap.add_argument("--layers", type=int, default=60)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
@@ -143,6 +244,8 @@ def main():
     ap.add_argument("--lib", default=None, help="another build of libomni_cdna4.so (with --teacache)")
     ap.add_argument("--only", default=None, help="with --teacache: the workload whose name starts with this (B or C)")
     a = ap.parse_args()
+    if a.edit:
+        return main_edit(a)
     if a.teacache is not None:
         return main_teacache(a)
     tr = QwenImageTransformer2DModel(num_layers=a.layers, device=DEV).init_random_(seed=1)

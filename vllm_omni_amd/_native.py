@@ -83,6 +83,14 @@ class AttnParams(C.Structure):
     ]
 
 
+class CfgEulerReq(C.Structure):
+    """omni_cfg_euler_req: one request of omni_cfg_euler_step_ragged (an array of these lives in DEVICE memory)."""
+    _fields_ = [
+        ("lat_row", C.c_int32), ("rows", C.c_int32), ("pos_row", C.c_int32), ("neg_row", C.c_int32),
+        ("dst_row", C.c_int32 * 2), ("dt_index", C.c_int32), ("cfg_scale", C.c_float),
+    ]
+
+
 class ConvParams(C.Structure):
     _fields_ = [
         ("x", c_bf16_p), ("w", c_bf16_p), ("bias", c_bf16_p), ("gamma", c_bf16_p), ("res", c_bf16_p), ("y", c_bf16_p),
@@ -222,11 +230,21 @@ PROTOTYPES = {
                                       c_bf16_p, C.c_void_p]),
 }
 
+# Entry points added to ABI v14 after its first release.  The exported FUNCTIONS of a version are fixed (PROTOTYPES: exactly what
+# `nm -D` lists as text), so such an entry point is exported as a const function POINTER of the same name, announced by a
+# capability bit of `omni_features()`; a C caller calls it like a function, `lib()` binds the pointer's target with the same
+# restype / argtypes discipline as PROTOTYPES.  name -> (restype, argtypes, feature bit)
+FEATURE_PROTOTYPES = {
+    "omni_cfg_euler_step_ragged": (C.c_int, [c_bf16_p, C.c_int32, c_bf16_p, C.c_int32, c_bf16_p, C.c_int32, C.c_void_p, C.c_int32,
+                                             C.c_int32, C.c_int32, c_f32_p, C.c_int32, C.c_int32, C.c_void_p], 4),
+}
+
 # symbols a library of the SAME ABI version may lack: they were added together with a field that went into former struct
 # padding, which keeps the version.  `features()` is how callers ask.
 OPTIONAL_SYMBOLS = ("omni_features",)
 FEATURE_ATTN_F16 = 1                              # OMNI_FEATURE_ATTN_F16
 FEATURE_TEACACHE_RAGGED = 2                       # OMNI_FEATURE_TEACACHE_RAGGED
+FEATURE_CFG_EULER_RAGGED = 4                      # OMNI_FEATURE_CFG_EULER_RAGGED: omni_cfg_euler_step_ragged is exported
 ELEM_BF16, ELEM_F16 = 0, 1                        # omni_attn_params.elem_type
 
 _lib = None
@@ -255,6 +273,12 @@ def lib() -> C.CDLL:
                 raise OmniNativeError(f"{LIB_PATH} does not export {name}") from e
             fn.restype = res
             fn.argtypes = args
+        for name, (res, args, _bit) in FEATURE_PROTOTYPES.items():
+            try:
+                entry = C.c_void_p.in_dll(dll, name).value      # the exported object is a POINTER to the function
+            except ValueError:
+                continue                                         # optional: callers ask features() first
+            setattr(dll, name, C.CFUNCTYPE(res, *args)(entry))
         got = dll.omni_abi_version()
         if got != ABI_VERSION:
             raise OmniNativeError(f"ABI mismatch: library {got}, binding {ABI_VERSION}")

@@ -585,20 +585,12 @@ __global__ void timestep_sinusoid_kernel(const float* __restrict__ t, int B, int
 // CFG combine + norm rescale + Euler update on [rows, 64] bf16: 8 lanes per row.
 // bytes/row = 3 reads + 1 write of 128 B.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void cfg_euler_kernel(const uint16_t* __restrict__ pos,
-                                                        const uint16_t* __restrict__ neg,
-                                                        uint16_t* __restrict__ lat, int rows, float cfg_scale,
-                                                        const float* __restrict__ dt, int dt_rows_per_item, int normalize) {
-  const int sub = threadIdx.x & 7;
-  const int row = blockIdx.x * 32 + (threadIdx.x >> 3);
-  if (row >= rows) return;
-  const int64_t off = (int64_t)row * 64 + sub * 8;
-  float p[8], x[8], pred[8];
-  unpack8(*reinterpret_cast<const u32x4_t*>(pos + off), p);
-  unpack8(*reinterpret_cast<const u32x4_t*>(lat + off), x);
-  if (neg) {
-    float n[8];
-    unpack8(*reinterpret_cast<const u32x4_t*>(neg + off), n);
+// One row's arithmetic on its 8 lanes (8 channels per lane): shared by the two kernels below, so that a request updated by the
+// ragged kernel gets the bits the plain kernel gives it.  has_neg false: no CFG (pred = pos, n is not read).
+__device__ __forceinline__ void cfg_euler_row(const float (&p)[8], const float (&n)[8], bool has_neg, const float (&x)[8],
+                                              float cfg_scale, float d, int normalize, float (&o)[8]) {
+  float pred[8];
+  if (has_neg) {
     float pp = 0.f, cc = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -615,11 +607,75 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(const uint16_t* __restri
 #pragma unroll
     for (int i = 0; i < 8; ++i) pred[i] = p[i];
   }
-  const float d = dt_rows_per_item > 0 ? dt[row / dt_rows_per_item] : dt[0];
-  float o[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) o[i] = x[i] + d * pred[i];
+}
+
+__global__ __launch_bounds__(256) void cfg_euler_kernel(const uint16_t* __restrict__ pos,
+                                                        const uint16_t* __restrict__ neg,
+                                                        uint16_t* __restrict__ lat, int rows, float cfg_scale,
+                                                        const float* __restrict__ dt, int dt_rows_per_item, int normalize) {
+  const int sub = threadIdx.x & 7;
+  const int row = blockIdx.x * 32 + (threadIdx.x >> 3);
+  if (row >= rows) return;
+  const int64_t off = (int64_t)row * 64 + sub * 8;
+  float p[8], x[8], n[8], o[8];
+  unpack8(*reinterpret_cast<const u32x4_t*>(pos + off), p);
+  unpack8(*reinterpret_cast<const u32x4_t*>(lat + off), x);
+  if (neg) unpack8(*reinterpret_cast<const u32x4_t*>(neg + off), n);
+  const float d = dt_rows_per_item > 0 ? dt[row / dt_rows_per_item] : dt[0];
+  cfg_euler_row(p, n, neg != nullptr, x, cfg_scale, d, normalize, o);
   *reinterpret_cast<u32x4_t*>(lat + off) = pack8(o);
+}
+
+// The same update for R requests of DIFFERENT row counts in one launch (omni_cfg_euler_step_ragged).  Block b owns the 32
+// "virtual" rows [32 b, 32 b + 32) of the concatenation of all requests' target rows; a row finds its request by a walk over
+// the row counts (staged in LDS once per block; R <= 64), so request boundaries may fall anywhere inside a block.  The
+// predictions are read where the forward wrote them (a request's first `rows` rows of its item, whatever follows them), and
+// the new row is also stored to up to two rows of the forward's INPUT buffer.  A request whose ranges leave one of the three
+// buffers is skipped whole: nothing is ever read or written outside [0, n_*_rows).
+__global__ __launch_bounds__(256) void cfg_euler_ragged_kernel(const uint16_t* __restrict__ pred, uint16_t* __restrict__ lat,
+                                                               uint16_t* __restrict__ lat_in,
+                                                               const omni_cfg_euler_req* __restrict__ reqs, int R, int total_rows,
+                                                               int n_lat_rows, int n_pred_rows, int n_in_rows,
+                                                               const float* __restrict__ dt, int n_dt, int normalize) {
+  __shared__ int s_rows[64];
+  if ((int)threadIdx.x < R) {
+    const int n = reqs[threadIdx.x].rows;
+    s_rows[threadIdx.x] = n > 0 ? n : 0;
+  }
+  __syncthreads();
+  const int sub = threadIdx.x & 7;
+  int v = blockIdx.x * 32 + (threadIdx.x >> 3);
+  if (v >= total_rows) return;
+  int r = 0;
+  for (; r < R; ++r) {
+    const int n = s_rows[r];
+    if (v < n) break;
+    v -= n;
+  }
+  if (r >= R) return;                                          // behind the last request (total_rows above the real sum)
+  const omni_cfg_euler_req* __restrict__ q = reqs + r;      // (fields into scalars: a local copy of the record would index
+  const int rows = q->rows, lat_row = q->lat_row, pos_row = q->pos_row, neg_row = q->neg_row;   //  dst_row[] in scratch)
+  const int dst0 = q->dst_row[0], dst1 = q->dst_row[1], dt_index = q->dt_index;
+  const float cfg_scale = q->cfg_scale;
+  const auto inside = [](int first, int count, int limit) { return first >= 0 && count <= limit && first <= limit - count; };
+  const bool has_neg = neg_row >= 0;
+  if (!inside(lat_row, rows, n_lat_rows) || !inside(pos_row, rows, n_pred_rows) ||
+      (has_neg && !inside(neg_row, rows, n_pred_rows)) || dt_index < 0 || dt_index >= n_dt)
+    return;
+  if ((dst0 >= 0 && !inside(dst0, rows, n_in_rows)) || (dst1 >= 0 && !inside(dst1, rows, n_in_rows))) return;
+  const int lane8 = sub * 8;
+  const int64_t l_off = ((int64_t)lat_row + v) * 64 + lane8;
+  float p[8], x[8], n[8], o[8];
+  unpack8(*reinterpret_cast<const u32x4_t*>(pred + ((int64_t)pos_row + v) * 64 + lane8), p);
+  unpack8(*reinterpret_cast<const u32x4_t*>(lat + l_off), x);
+  if (has_neg) unpack8(*reinterpret_cast<const u32x4_t*>(pred + ((int64_t)neg_row + v) * 64 + lane8), n);
+  cfg_euler_row(p, n, has_neg, x, cfg_scale, dt[dt_index], normalize, o);
+  const u32x4_t packed = pack8(o);
+  *reinterpret_cast<u32x4_t*>(lat + l_off) = packed;
+  if (dst0 >= 0) *reinterpret_cast<u32x4_t*>(lat_in + ((int64_t)dst0 + v) * 64 + lane8) = packed;
+  if (dst1 >= 0) *reinterpret_cast<u32x4_t*>(lat_in + ((int64_t)dst1 + v) * 64 + lane8) = packed;
 }
 
 }  // namespace
@@ -1100,6 +1156,31 @@ extern "C" int omni_cfg_euler_step(const omni_bf16* pos, const omni_bf16* neg, o
                                    omni_stream stream) {
   return omni_cfg_euler_step_ex(pos, neg, latents, rows, C, true_cfg_scale, dt, dt_rows_per_item, 1, stream);
 }
+
+static int cfg_euler_step_ragged(const omni_bf16* pred, int32_t n_pred_rows, omni_bf16* latents, int32_t n_lat_rows,
+                                 omni_bf16* lat_in, int32_t n_in_rows, const omni_cfg_euler_req* reqs, int32_t R,
+                                 int32_t total_rows, int32_t C, const float* dt, int32_t n_dt, int32_t normalize,
+                                 omni_stream stream) {
+  if (!pred || !latents || !lat_in || !reqs || !dt) return OMNI_ERR_BAD_ARG;
+  if (n_pred_rows <= 0 || n_lat_rows <= 0 || n_in_rows <= 0 || R <= 0 || total_rows <= 0 || n_dt <= 0) return OMNI_ERR_BAD_ARG;
+  if (total_rows > n_lat_rows) return OMNI_ERR_BAD_ARG;         // the requests' rows are disjoint rows of `latents`
+  if (C != 64 || R > 64) return OMNI_ERR_UNSUPPORTED;
+  if (!omni_aligned16(pred) || !omni_aligned16(latents) || !omni_aligned16(lat_in) || (reinterpret_cast<uintptr_t>(reqs) & 3u) ||
+      (reinterpret_cast<uintptr_t>(dt) & 3u))
+    return OMNI_ERR_ALIGN;
+  hipLaunchKernelGGL(cfg_euler_ragged_kernel, dim3((total_rows + 31) / 32), dim3(256), 0, static_cast<hipStream_t>(stream), pred,
+                     latents, lat_in, reqs, R, total_rows, n_lat_rows, n_pred_rows, n_in_rows, dt, n_dt, normalize ? 1 : 0);
+  OMNI_CHECK_LAUNCH();
+  return OMNI_OK;
+}
+
+// exported as a const pointer, not as a function: see the header (the exported functions of ABI v14 are fixed).  Host pass only:
+// a namespace-scope const would otherwise be emitted for the device as well, where its initialiser does not exist
+#if !defined(__HIP_DEVICE_COMPILE__)
+extern "C" int (*const omni_cfg_euler_step_ragged)(const omni_bf16*, int32_t, omni_bf16*, int32_t, omni_bf16*, int32_t,
+                                                   const omni_cfg_euler_req*, int32_t, int32_t, int32_t, const float*, int32_t,
+                                                   int32_t, omni_stream) = cfg_euler_step_ragged;
+#endif
 
 int omni_internal_silu_bf16(omni_bf16* dst, const omni_bf16* src, int64_t n, void* stream) {
   if (!dst || !src || n <= 0) return OMNI_ERR_BAD_ARG;

@@ -177,6 +177,42 @@ def build_ragged_batch(txt_lens: list[int], grid, temb_rows: list[int] | None = 
                        joint_pos=joint_pos)
 
 
+# ---- the step update of a group whose requests differ in target rows AND carry condition rows (Edit / Edit-Plus): host model
+# of omni_cfg_euler_req (include/omni_cdna4.h).  Item order of the forward: pos_0..pos_{R-1}, neg_0..neg_{R-1}; item i holds
+# [target rows of its request ; that request's condition rows].
+CFG_EULER_RAGGED_MAX_REQS = 64
+CFG_EULER_REQ_DTYPE = np.dtype([("lat_row", "<i4"), ("rows", "<i4"), ("pos_row", "<i4"), ("neg_row", "<i4"),
+                                ("dst_row", "<i4", (2,)), ("dt_index", "<i4"), ("cfg_scale", "<f4")])
+
+
+def ragged_step_descriptors(target_rows: list[int], cond_rows: list[int], do_cfg: bool, scales: list[float]) -> dict:
+    """Row layout of one step of R requests, request r with target_rows[r] latent rows and cond_rows[r] condition rows:
+      lat_off   [R + 1]        request r's rows of the latent state `lat`  (the state holds target rows only)
+      item_off  [n_items + 1]  item i's rows of the forward's input `lat_in` and output `pred`: target rows, then condition rows
+      reqs      [R] omni_cfg_euler_req records: where request r's predictions start in `pred` (the first target_rows[r] rows of
+                its items), where its updated rows go in `lat_in` (the same rows: the next step's input), its dt entry r, its scale
+      total_rows               sum of the target rows (sizes the kernel launch)."""
+    R = len(target_rows)
+    if not 0 < R <= CFG_EULER_RAGGED_MAX_REQS:
+        raise ValueError(f"{R} requests: the ragged step update takes 1 .. {CFG_EULER_RAGGED_MAX_REQS}")
+    if len(cond_rows) != R or len(scales) != R:
+        raise ValueError("one condition row count and one scale per request")
+    if any(int(s) < 1 for s in target_rows) or any(int(c) < 0 for c in cond_rows):
+        raise ValueError("every request needs at least one target row (condition rows may be none)")
+    lat_off = [0]
+    for s in target_rows:
+        lat_off.append(lat_off[-1] + int(s))
+    item_off = [0]
+    for _ in range(2 if do_cfg else 1):
+        for s, c in zip(target_rows, cond_rows):
+            item_off.append(item_off[-1] + int(s) + int(c))
+    reqs = np.zeros(R, dtype=CFG_EULER_REQ_DTYPE)
+    for r in range(R):
+        neg = item_off[R + r] if do_cfg else -1
+        reqs[r] = (lat_off[r], int(target_rows[r]), item_off[r], neg, (item_off[r], neg), r, float(scales[r]))
+    return dict(lat_off=lat_off, item_off=item_off, reqs=reqs, total_rows=lat_off[-1])
+
+
 # ---- the compact attention grid for items of unequal length: host model of csrc/common.h (omni_attn_compact_slots,
 # omni_attn_slot_lookup).  The kernels do this on the device; these functions state the same rule for tests and tools.
 ATTN_COMPACT_MAX_ITEMS = 64

@@ -137,6 +137,10 @@ class OmniDiffusionConfig:
     mixed_step_batch_teacache: bool = False  # NEW, opt-in, only together with mixed_step_batch: mixed groups also form when
                                      # TeaCache is configured (its kernels address every item by its own image-row range,
                                      # OMNI_FEATURE_TEACACHE_RAGGED).  Off: TeaCache keeps the grid in the batch key
+    mixed_step_batch_edit: bool = False  # NEW, opt-in, only together with mixed_step_batch: Edit / Edit-Plus requests (condition-
+                                     # image rows behind the target rows) of different output sizes, condition grids and
+                                     # scales share a DiT forward; one ragged CFG + Euler launch per step
+                                     # (omni_cfg_euler_step_ragged).  Off: such samples keep grid and scale in the key
     max_step_tokens: int | None = None  # NEW: admission bound next to max_step_batch — the largest sum of image rows x CFG
                                      # branches one forward may hold (the oldest sample always runs, alone if need be)
     # ---- the reference's remaining fields (data.py:255-360), so that a config written for it constructs here unchanged.
@@ -205,6 +209,9 @@ class OmniDiffusionConfig:
             self.dtype = known
         if self.mixed_step_batch_teacache and not self.mixed_step_batch:
             raise ValueError("mixed_step_batch_teacache=True extends mixed_step_batch and means nothing without it: set "
+                             "mixed_step_batch=True as well")
+        if self.mixed_step_batch_edit and not self.mixed_step_batch:
+            raise ValueError("mixed_step_batch_edit=True extends mixed_step_batch and means nothing without it: set "
                              "mixed_step_batch=True as well")
         if self.cache_backend is None:
             self.cache_backend = "none"

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from .... import ops
-from ...batch import build_ragged_batch
+from ...batch import build_ragged_batch, ragged_step_descriptors
 from ...data import DiffusionOutput, OmniDiffusionConfig, require_fused_bf16
 from ...request import OmniDiffusionRequest
 from .autoencoder_kl_qwenimage import AutoencoderKLQwenImage
@@ -549,8 +549,12 @@ class QwenImagePipeline(nn.Module):
         `od_config.mixed_step_batch` plain text-to-image samples of ANY grid and scale share a key (the kernels address rows
         through per-item maps; the CFG + Euler update runs per request).  The grid stays in the key for samples that carry
         condition rows (Edit / Edit-Plus / Layered: multi-entry grids) and, unless `od_config.mixed_step_batch_teacache` is
-        set as well, whenever TeaCache is configured."""
+        set as well, whenever TeaCache is configured.  With `od_config.mixed_step_batch_edit` on top, Edit / Edit-Plus samples
+        (condition rows, plain-triple grid entries, no `t_cond`) drop grid and scale as well, under a key of their own: their
+        step update is one ragged launch (`omni_cfg_euler_step_ragged`).  Layered samples keep their key."""
         sm = a.sample
+        if self._mixed_edit(sm):
+            return ("mixed_edit", sm["do_cfg"], sm.get("cfg_normalize", True), sm.get("t_cond"))
         if (getattr(self.od_config, "mixed_step_batch", False) and sm.get("cond") is None
                 and (self._mixed_teacache() or not self._teacache_configured())):
             return ("mixed", sm["do_cfg"], sm.get("cfg_normalize", True), sm.get("t_cond"))
@@ -562,6 +566,20 @@ class QwenImagePipeline(nn.Module):
     def _mixed_teacache(self) -> bool:
         """May a mixed group run with TeaCache?  (Both opt-ins: the TeaCache kernels then take items of unequal image rows.)"""
         return bool(getattr(self.od_config, "mixed_step_batch", False) and getattr(self.od_config, "mixed_step_batch_teacache", False))
+
+    def _mixed_edit(self, sm: dict) -> bool:
+        """Does this sample take the mixed Edit path?  All three of: both opt-ins; an Edit / Edit-Plus sample (condition rows
+        behind the target rows, every grid entry a plain (frames, h, w) triple, no additional_t_cond: not the Layered
+        variant); TeaCache either off or allowed in mixed groups."""
+        cfg = self.od_config
+        if not (getattr(cfg, "mixed_step_batch", False) and getattr(cfg, "mixed_step_batch_edit", False)):
+            return False
+        grid = sm.get("grid")
+        if sm.get("cond") is None or sm.get("t_cond") is not None or not grid:
+            return False
+        if not all(isinstance(g, (tuple, list)) and len(g) == 3 for g in grid):
+            return False
+        return self._mixed_teacache() or not self._teacache_configured()
 
     # A "serve state" = everything one composition of a running batch needs, allocated ONCE: the static input / output
     # buffers of the forward, the ragged-batch descriptor, the per-request timestep / dt vectors, the TeaCache device state
@@ -581,6 +599,8 @@ class QwenImagePipeline(nn.Module):
         # a MIXED group: requests on different token grids and / or with different true-CFG scales in one forward
         grids = [tuple(a.sample["grid"]) for a in group]
         cfgs = [float(a.sample["cfg"]) for a in group]
+        if all(self._mixed_edit(a.sample) for a in group):
+            return self._serve_state_edit(group, grids, cfgs, lens)
         mixed = len(set(grids)) > 1 or len(set(cfgs)) > 1
         if mixed:
             if any(a.sample["do_cfg"] != do_cfg for a in group):
@@ -633,6 +653,10 @@ class QwenImagePipeline(nn.Module):
             from ...cache.teacache.native import TeaCacheDeviceState
 
             st["tc"] = TeaCacheDeviceState(tcfg, rb, tr.inner_dim, dev)
+        self._keep_serve_state(key, st)
+        return st
+
+    def _keep_serve_state(self, key, st: dict) -> None:
         if len(self._serve_states) >= 8:                      # evict: every resident sample goes back to its own tensors
             for old in self._serve_states.values():
                 for occ in old["members"]:
@@ -640,7 +664,67 @@ class QwenImagePipeline(nn.Module):
                         self._export_sample(occ)
             self._serve_states.clear()
         self._serve_states[key] = st
+
+    def _serve_state_edit(self, group: list, grids: list, cfgs: list, lens: list) -> dict:
+        """The serve state of an Edit / Edit-Plus group under `mixed_step_batch_edit`: request r has S_r target rows and
+        S_c,r condition rows of its own.  `lat` holds the target rows of all slots; item i of the forward owns the rows
+        [item_off[i], item_off[i + 1]) of `lat_in` and `pred`: S_r target rows, then the condition rows.  The step update is ONE
+        launch of omni_cfg_euler_step_ragged, which also writes the new latents into the target rows of `lat_in`: no `pred_c`,
+        no per-step lat -> lat_in copy.  The condition rows of `lat_in` are written when a sample takes its slot, and whoever
+        writes `lat` outside the kernel refreshes the slot's `lat_in` target rows (`_import_sample`, `_refresh_lat_in`)."""
+        tr, dev = self.transformer, self.device
+        sm0 = group[0].sample
+        R, do_cfg = len(group), sm0["do_cfg"]
+        if any(a.sample["do_cfg"] != do_cfg for a in group):
+            raise NotImplementedError("a mixed step-batch cannot combine requests with and without true-CFG")
+        tcfg = getattr(tr, "teacache", None)
+        use_tab = bool(getattr(self.od_config, "precompute_modulation", True))
+        S_list = [int(a.state["lat"].shape[0]) for a in group]
+        Sc_list = [int(a.state["cond"].shape[0]) for a in group]
+        key = ("mixed_edit", tuple(lens), tuple(grids), do_cfg, tuple(cfgs), R, sm0.get("cfg_normalize", True), use_tab)
+        if tcfg is not None:
+            key += ((tcfg.rel_l1_thresh, tuple(tcfg.coefficients)),)
+        st = self._serve_states.get(key)
+        if st is not None:
+            return st
+        n_items, Cl = (2 if do_cfg else 1) * R, tr.in_channels
+        rb = build_ragged_batch(lens, grids * (2 if do_cfg else 1), temb_rows=list(range(R)) * (2 if do_cfg else 1))
+        lay = ragged_step_descriptors(S_list, Sc_list, do_cfg, cfgs)
+        if lay["item_off"] != rb.img_offsets:
+            raise ValueError(f"latent / condition rows {S_list} / {Sc_list} do not match the token grids {grids}")
+        offs = [0]
+        for t in lens:
+            offs.append(offs[-1] + t)
+        st = dict(key=key, R=R, S=None, S_c=None, do_cfg=do_cfg, cfg=None, n_items=n_items, rb=rb, txt_off=offs,
+                  mixed=len(set(grids)) > 1 or len(set(cfgs)) > 1, ragged=True, cfgs=cfgs, img_off=lay["lat_off"],
+                  n_lat=lay["total_rows"], S_list=S_list, Sc_list=Sc_list, item_off=lay["item_off"],
+                  reqs=torch.from_numpy(lay["reqs"].view("<i4").reshape(R, 8).copy()).to(dev),
+                  cfg_normalize=bool(sm0.get("cfg_normalize", True)), t_cond=None, temb_add=None,
+                  prepared=tr.prepare_batch(rb), members=[None] * R, graph=None, gen=None,
+                  lat=torch.zeros(lay["total_rows"], Cl, dtype=BF16, device=dev),
+                  lat_in=torch.zeros(rb.n_img_rows, Cl, dtype=BF16, device=dev),
+                  pred=torch.empty(rb.n_img_rows, Cl, dtype=BF16, device=dev), pred_c=None,
+                  prompt=torch.zeros(sum(lens), tr.joint_attention_dim, dtype=BF16, device=dev),
+                  sig=torch.zeros(R, dtype=torch.float32, device=dev), dt=torch.zeros(R, dtype=torch.float32, device=dev),
+                  sig_tab=torch.zeros(R, self.SERVE_MAX_STEPS, dtype=torch.float32, device=dev),
+                  dt_tab=torch.zeros(R, self.SERVE_MAX_STEPS, dtype=torch.float32, device=dev),
+                  step_idx=torch.zeros(R, dtype=torch.int64, device=dev), tc=None,
+                  mod=(torch.zeros(len(tr.transformer_blocks), 2, R, 6 * tr.inner_dim, dtype=BF16, device=dev) if use_tab else None))
+        if tcfg is not None:
+            from ...cache.teacache.native import TeaCacheDeviceState
+
+            st["tc"] = TeaCacheDeviceState(tcfg, rb, tr.inner_dim, dev)
+        self._keep_serve_state(key, st)
         return st
+
+    @staticmethod
+    def _refresh_lat_in(st: dict, slots=None) -> None:
+        """Ragged (mixed Edit) state: copy the latents of `slots` (default: all) into the target rows of their items of
+        `lat_in`.  Per step the kernel does this; needed wherever something else wrote `lat`."""
+        R, lo, io = st["R"], st["img_off"], st["item_off"]
+        for r in (range(R) if slots is None else slots):
+            for i in ([r, R + r] if st["do_cfg"] else [r]):
+                st["lat_in"][io[i]:io[i] + st["S_list"][r]].copy_(st["lat"][lo[r]:lo[r + 1]])
 
     def _export_sample(self, a) -> None:
         """Copy a sample's latents (and TeaCache history) out of its home slot; the slot becomes free."""
@@ -673,7 +757,12 @@ class QwenImagePipeline(nn.Module):
         st["prompt"][off[r]:off[r + 1]].copy_(a.state["pos"])
         if do_cfg:
             st["prompt"][off[R + r]:off[R + r + 1]].copy_(a.state["neg"])
-        if S_c:                                              # Edit: the condition rows of this sample's item(s) never change
+        if st.get("ragged"):                                 # mixed Edit: target rows now, condition rows once and for all
+            io, S_r = st["item_off"], st["S_list"][r]
+            self._refresh_lat_in(st, [r])
+            for i in ([r, R + r] if do_cfg else [r]):
+                st["lat_in"][io[i] + S_r:io[i + 1]].copy_(a.state["cond"])
+        elif S_c:                                            # Edit: the condition rows of this sample's item(s) never change
             li = st["lat_in"].view(st["n_items"], S + S_c, -1)
             li[r, S:].copy_(a.state["cond"])
             if do_cfg:
@@ -694,6 +783,14 @@ class QwenImagePipeline(nn.Module):
         idx = st["step_idx"].clamp(max=self.SERVE_MAX_STEPS - 1).view(R, 1)
         st["sig"].copy_(st["sig_tab"].gather(1, idx).view(R))
         st["dt"].copy_(st["dt_tab"].gather(1, idx).view(R))
+        if st.get("ragged"):
+            # mixed Edit group: `lat_in` already holds every slot's latents (the previous step's kernel, or whoever wrote `lat`,
+            # put them there) and its condition rows; ONE launch reads each request's predictions in place and updates both
+            tr.forward_ragged(st["prepared"], lat_in, st["prompt"], st["sig"], out=pred, teacache=st["tc"], temb_add=None,
+                              mod_table=st["mod"])
+            ops.cfg_euler_step_ragged_(lat, pred, lat_in, st["reqs"], R, n_lat, st["dt"], normalize=st["cfg_normalize"])
+            st["step_idx"].add_(1)
+            return
         if S_c:
             li = lat_in.view(n_items, S + S_c, Cl)
             li[:R, :S].copy_(lat.view(R, S, Cl))
@@ -745,7 +842,7 @@ class QwenImagePipeline(nn.Module):
                 st["mod"][:, :, r].copy_(a.state["mod_tab"][:, :, min(a.step, a.n_steps - 1)])
         tr.do_true_cfg = st["do_cfg"]
         self.last_teacache_state = st["tc"]
-        if not self._use_graph((2 if st["do_cfg"] else 1) * st["n_lat"]):
+        if not self._use_graph(st["rb"].n_img_rows if st.get("ragged") else (2 if st["do_cfg"] else 1) * st["n_lat"]):
             self._serve_step_body(st)
             return
         tr._native_weights()
@@ -767,6 +864,8 @@ class QwenImagePipeline(nn.Module):
             st["graph"], st["gen"] = g, tr._native_gen
             st["keepalive"] = (st["prepared"], tr._workspace, tr._native)
             st["lat"].copy_(saved_lat)
+            if st.get("ragged"):
+                self._refresh_lat_in(st)                     # the warm-up / capture steps advanced the input rows as well
             st["step_idx"].copy_(saved_idx)
             if saved_tc is not None:
                 for i, sv in enumerate(saved_tc):

@@ -145,22 +145,30 @@ class ContinuousStepBatcher:
                     break
                 group.append(a)
                 used += t
-        if all(a.sample.get("lat") is not None for a in group) and len({self._rows(a) for a in group}) > 1:
-            group = sorted(group, key=lambda a: (-self._rows(a), a.seq))
+        if all(a.sample.get("lat") is not None for a in group) and len({self._total_rows(a) for a in group}) > 1:
+            group = sorted(group, key=lambda a: (-self._total_rows(a), a.seq))
         return group
 
     @staticmethod
     def _rows(a: ActiveSample) -> int:
-        """Image rows of the sample (`sample["lat"]`: [rows, channels]).  Only consulted when a group can differ in size or a token
+        """Target image rows of the sample (`sample["lat"]`: [rows, channels]).  Only consulted when a group can differ in size or a token
         budget is set; a pipeline that uses either must put the latents into its samples."""
         lat = a.sample.get("lat")
         if lat is None:
             raise ValueError("max_step_tokens / mixed step batches need the sample's latents (sample['lat']) to size it")
         return int(lat.shape[0])
 
+    def _total_rows(self, a: ActiveSample) -> int:
+        """Rows of one item of the sample in a forward.  With the pipeline's `mixed_step_batch_edit` the condition-image rows
+        count as well (an Edit request near 1024^2 carries as many of them as target rows); otherwise the image rows alone."""
+        cond = a.sample.get("cond")
+        if cond is None or not getattr(getattr(self.pipeline, "od_config", None), "mixed_step_batch_edit", False):
+            return self._rows(a)
+        return self._rows(a) + int(cond.shape[0])
+
     def _tokens(self, a: ActiveSample) -> int:
         """Image rows x CFG branches: what the sample adds to a forward."""
-        return self._rows(a) * (2 if a.sample.get("do_cfg") else 1)
+        return self._total_rows(a) * (2 if a.sample.get("do_cfg") else 1)
 
     def step(self) -> list[tuple[Any, Any]]:
         """Advance one group of active samples by one denoising step; return finished (tag, output)s."""

@@ -413,6 +413,27 @@ def cfg_euler_step_(latents, pos, neg, true_cfg_scale: float, dt: torch.Tensor, 
     return latents
 
 
+def cfg_euler_step_ragged_(latents, pred, lat_in, reqs, n_reqs: int, total_rows: int, dt: torch.Tensor, normalize: bool = True):
+    """omni_cfg_euler_step_ragged: ONE launch updates the `n_reqs` requests that `reqs` describes (int32 [n_reqs, 8] on the
+    device: the bytes of omni_cfg_euler_req, built by diffusion/batch.py `ragged_step_descriptors`), each with its own row
+    count, scale and dt entry.  `latents` [*, 64] is updated in place from the prediction rows of `pred` [*, 64]; the new rows
+    are also written to their rows of `lat_in` [*, 64], the next forward's input.  `total_rows`: the requests' rows summed."""
+    if not N.features() & N.FEATURE_CFG_EULER_RAGGED:
+        raise N.OmniNativeError("this libomni_cdna4.so does not report OMNI_FEATURE_CFG_EULER_RAGGED: it has no "
+                                "omni_cfg_euler_step_ragged (the step update of mixed Edit groups)")
+    for t, name in ((latents, "latents"), (pred, "pred"), (lat_in, "lat_in")):
+        if t.dim() != 2 or not t.is_contiguous():
+            raise N.OmniNativeError(f"cfg_euler_step_ragged_: {name} must be a contiguous [rows, 64] tensor")
+    if reqs.dim() != 2 or reqs.shape[1] != 8 or not reqs.is_contiguous() or reqs.shape[0] < n_reqs:
+        raise N.OmniNativeError("cfg_euler_step_ragged_: reqs must be a contiguous int32 [>= n_reqs, 8] tensor")
+    N.check(N.lib().omni_cfg_euler_step_ragged(_p(pred, name="pred"), pred.shape[0], _p(latents, name="latents"), latents.shape[0],
+                                               _p(lat_in, name="lat_in"), lat_in.shape[0], _p(reqs, torch.int32, "reqs"), n_reqs,
+                                               total_rows, latents.shape[1], _p(dt, torch.float32, "dt"), dt.numel(),
+                                               1 if normalize else 0, _stream()),
+            "omni_cfg_euler_step_ragged")
+    return latents
+
+
 def vae_conv2d(x, w, bias=None, *, gamma=None, silu=True, res=None, upsample2x=False, downsample2x=False, clamp=None,
                out=None, x_bordered=False, y_bordered=False, norm_gamma=None, norm_silu=True, keep_raw=True):
     """NHWC bf16 conv (3x3 pad 1 or 1x1): x [B,H,W,Cin], w [Cout,ks,ks,Cin].  downsample2x: the encoder's zero-pad
