@@ -54,6 +54,7 @@ const char* omni_status_string(int status);
 #define OMNI_FEATURE_TEACACHE_RAGGED 2u /* omni_dit_forward's TeaCache kernels address every item by its own image-row range:
                                          * the items of a batch with omni_dit_batch.teacache set may differ in image rows */
 #define OMNI_FEATURE_CFG_EULER_RAGGED 4u /* the library exports omni_cfg_euler_step_ragged: a function pointer, see there */
+#define OMNI_FEATURE_LORA_MERGE 8u /* the library exports omni_lora_merge: a function pointer, see there */
 uint32_t omni_features(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -458,6 +459,34 @@ extern int (*const omni_cfg_euler_step_ragged)(const omni_bf16* pred, int32_t n_
                                                int32_t n_lat_rows, omni_bf16* lat_in, int32_t n_in_rows,
                                                const omni_cfg_euler_req* reqs, int32_t R, int32_t total_rows, int32_t C,
                                                const float* dt, int32_t n_dt, int32_t normalize, omni_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * LoRA merge: one row range of one weight matrix receives its low-rank update, on the device (optional symbol of ABI v14:
+ * ask omni_features() & OMNI_FEATURE_LORA_MERGE).  The reference has no implementation to mirror (only the config fields,
+ * data.py:280-286); this is the usual definition:
+ *   W_out[n, k] = bf16_rne( float(W_base[n, k]) + scale * sum_{r < R} float(up[n - row0, r]) * float(down[r, k]) )
+ * for n in [row0, row0 + rows); rows outside the range are neither read nor written.  fp32 accumulation on the matrix cores,
+ * `scale` applied in fp32 after the sum, ONE rounding to bf16; scale == 0 copies the base bits.  W_out may be W_base (each
+ * element is read once and written once by the same lane); any other overlap of the two is undefined.
+ *   W     [N, K]: row-major with row pitch ldw (elements), or - w_k32_blocked = 1, the layout of omni_gemm_params.w_k32_blocked -
+ *         K32-blocked [K/32][N][32] (ldw ignored).  W_base and W_out share layout and pitch.
+ *   up    [rows, R] bf16 row-major, dense (lora_B / lora_up rows of the range);  down [R, K] bf16 row-major, dense (lora_A).
+ * Any R in 1..256 (the rank tail is masked inside the kernel), any row0 / rows inside [0, N).
+ * Status, before any launch: null pointer, N / K < 1, rows < 1, a range that leaves [0, N), ldw < K -> OMNI_ERR_BAD_ARG;
+ * K % 32 != 0, R < 1, R > 256 -> OMNI_ERR_UNSUPPORTED; a pointer not 16-byte aligned, ldw % 8 != 0 -> OMNI_ERR_ALIGN. */
+typedef struct omni_lora_merge_params {
+  const omni_bf16* w_base;
+  omni_bf16* w_out;
+  const omni_bf16* up;
+  const omni_bf16* down;
+  int32_t N, K, R;
+  int32_t row0, rows;
+  int32_t w_k32_blocked;
+  int64_t ldw;
+  float scale;
+} omni_lora_merge_params;
+/* a const function POINTER like omni_cfg_euler_step_ragged, for the same reason */
+extern int (*const omni_lora_merge)(const omni_lora_merge_params* p, omni_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * VAE kernels (AutoencoderKLQwenImage.decode — and .encode for the Edit pipelines — for one frame,

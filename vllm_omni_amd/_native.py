@@ -91,6 +91,15 @@ class CfgEulerReq(C.Structure):
     ]
 
 
+class LoraMergeParams(C.Structure):
+    """omni_lora_merge_params: one row range of one weight matrix and its low-rank update (omni_lora_merge)."""
+    _fields_ = [
+        ("w_base", c_bf16_p), ("w_out", c_bf16_p), ("up", c_bf16_p), ("down", c_bf16_p),
+        ("N", C.c_int32), ("K", C.c_int32), ("R", C.c_int32), ("row0", C.c_int32), ("rows", C.c_int32),
+        ("w_k32_blocked", C.c_int32), ("ldw", C.c_int64), ("scale", C.c_float),
+    ]
+
+
 class ConvParams(C.Structure):
     _fields_ = [
         ("x", c_bf16_p), ("w", c_bf16_p), ("bias", c_bf16_p), ("gamma", c_bf16_p), ("res", c_bf16_p), ("y", c_bf16_p),
@@ -237,6 +246,7 @@ PROTOTYPES = {
 FEATURE_PROTOTYPES = {
     "omni_cfg_euler_step_ragged": (C.c_int, [c_bf16_p, C.c_int32, c_bf16_p, C.c_int32, c_bf16_p, C.c_int32, C.c_void_p, C.c_int32,
                                              C.c_int32, C.c_int32, c_f32_p, C.c_int32, C.c_int32, C.c_void_p], 4),
+    "omni_lora_merge": (C.c_int, [C.POINTER(LoraMergeParams), C.c_void_p], 8),
 }
 
 # symbols a library of the SAME ABI version may lack: they were added together with a field that went into former struct
@@ -245,6 +255,7 @@ OPTIONAL_SYMBOLS = ("omni_features",)
 FEATURE_ATTN_F16 = 1                              # OMNI_FEATURE_ATTN_F16
 FEATURE_TEACACHE_RAGGED = 2                       # OMNI_FEATURE_TEACACHE_RAGGED
 FEATURE_CFG_EULER_RAGGED = 4                      # OMNI_FEATURE_CFG_EULER_RAGGED: omni_cfg_euler_step_ragged is exported
+FEATURE_LORA_MERGE = 8                            # OMNI_FEATURE_LORA_MERGE: omni_lora_merge is exported
 ELEM_BF16, ELEM_F16 = 0, 1                        # omni_attn_params.elem_type
 
 _lib = None

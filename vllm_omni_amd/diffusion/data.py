@@ -141,6 +141,16 @@ class OmniDiffusionConfig:
                                      # image rows behind the target rows) of different output sizes, condition grids and
                                      # scales share a DiT forward; one ragged CFG + Euler launch per step
                                      # (omni_cfg_euler_step_ragged).  Off: such samples keep grid and scale in the key
+    lora_adapters: dict[str, str] | None = None  # NEW, opt-in: LoRA adapters by name -> path (.safetensors / .pt / .bin), loaded
+                                     # when the model is initialised; a request picks one with `OmniDiffusionRequest.lora`.
+                                     # NEW names on purpose: the reference's `lora_path` / `lora_nickname` / `lora_target_modules`
+                                     # (below) name a mechanism the reference never built - one adapter fixed at start-up, no
+                                     # defined behaviour to match - so they stay refused and the capability enters here
+                                     # (adapters are merged on the device into copies of the targeted matrices: DESIGN.md 6)
+    max_resident_loras: int = 1      # NEW: merged weight sets kept on the device (LRU) next to the base weights; re-activating
+                                     # a resident combination launches nothing
+    lora_switch_patience: int = 8    # NEW: forwards the step batcher lets a sample of a NON-resident adapter combination wait
+                                     # while resident combinations have work (a switch costs a pass over the targeted weights)
     max_step_tokens: int | None = None  # NEW: admission bound next to max_step_batch — the largest sum of image rows x CFG
                                      # branches one forward may hold (the oldest sample always runs, alone if need be)
     # ---- the reference's remaining fields (data.py:255-360), so that a config written for it constructs here unchanged.
@@ -213,6 +223,11 @@ class OmniDiffusionConfig:
         if self.mixed_step_batch_edit and not self.mixed_step_batch:
             raise ValueError("mixed_step_batch_edit=True extends mixed_step_batch and means nothing without it: set "
                              "mixed_step_batch=True as well")
+        if self.lora_adapters is not None and not (isinstance(self.lora_adapters, dict) and all(
+                isinstance(k, str) and (isinstance(v, (str, bytes)) or hasattr(v, "__fspath__")) for k, v in self.lora_adapters.items())):
+            raise TypeError("lora_adapters maps adapter names to file paths")
+        if int(self.max_resident_loras) < 1 or int(self.lora_switch_patience) < 0:
+            raise ValueError("max_resident_loras must be >= 1 and lora_switch_patience >= 0")
         if self.cache_backend is None:
             self.cache_backend = "none"
         if self.cache_backend not in ("none", "tea_cache", "teacache"):

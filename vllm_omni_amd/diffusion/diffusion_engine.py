@@ -214,6 +214,33 @@ class DiffusionEngine:
         res = self._rpc_results.pop(rid)
         return res[unique_reply_rank] if unique_reply_rank is not None else [res[r] for r in sorted(res)]
 
+    def add_lora(self, name: str, path: str, timeout: float | None = None) -> None:
+        """Load the LoRA adapter file `path` under `name` on EVERY worker; requests then pick it with
+        `OmniDiffusionRequest.lora`.  All workers or none: when one of them could not load it, the name is removed again from
+        those that did (also where it replaced an earlier adapter of that name), and this raises."""
+        try:
+            self._lora_rpc("add_lora", (name, path), timeout)
+        except RuntimeError:
+            self.collective_rpc("remove_lora", args=(name,), timeout=timeout)      # (errors of workers that never had it: ignored)
+            raise
+
+    def remove_lora(self, name: str, timeout: float | None = None) -> None:
+        """Forget the adapter `name` on every worker (its merged weight sets are freed).  An adapter that is still active on a
+        worker after its last request is deactivated there first.  While requests in flight name it, on any worker, this raises
+        and removes it NOWHERE: the workers are asked first, and a worker's inbox is served in order, so every request submitted
+        before this call has been seen by then."""
+        busy = self._lora_rpc("lora_in_use", (name,), timeout)
+        if any(busy):
+            raise RuntimeError(f"remove_lora({name!r}): {sum(busy)} sample(s) in flight use it")
+        self._lora_rpc("remove_lora", (name,), timeout)
+
+    def _lora_rpc(self, method: str, args: tuple, timeout: float | None) -> list:
+        res = self.collective_rpc(method, args=args, timeout=timeout)
+        errs = [r.error for r in res if isinstance(r, DiffusionOutput) and r.error]
+        if errs:
+            raise RuntimeError(f"{method}{args}: " + " | ".join(e.splitlines()[0] for e in errs))
+        return res
+
     def close(self, timeout_s: float = 30.0) -> None:
         if self._closed:
             return

@@ -69,6 +69,7 @@ class QwenImagePipeline(nn.Module):
         self.weights_sources: list = []
         self._step_state: dict = {}     # hipGraph + static buffers per step-batch shape
         self._serve_states: dict = {}   # the same for the continuous step batcher (denoise_one_step)
+        self._graph_gens: set = set()   # the pointer-table generations the captured graphs of ALL states were last pruned to
         # Ulysses sequence parallelism: set by the worker when parallel_config.ulysses_degree > 1 — the
         # process group of this rank's SP group; every rank of the group then runs the SAME requests in lockstep
         self.sp_group, self.sp_degree = None, 1
@@ -248,7 +249,7 @@ class QwenImagePipeline(nn.Module):
                 step(sig_in[i:i + 1], dt_dev[i:i + 1])
             return list(lat.clone().view(R, S, -1).unbind(0))
         tr._native_weights()      # (re)build the pointer table NOW: `_native_gen` then names the storages a replay would read
-        if st["graph"] is None or st.get("gen") != tr._native_gen:
+        if self._captured(st) is None:
             # warm-up on a side stream (lazy initialisation inside the native library: function attributes, workspace),
             # then capture; the warm-up step advances `lat`, so the real inputs are restored afterwards
             saved = lat.clone()
@@ -261,11 +262,9 @@ class QwenImagePipeline(nn.Module):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 step(st["sig"], st["dt"])
-            st["graph"] = g
+            self._keep_captured(st, g, prepared)
             if tc is not None:
                 tc.reset()                                   # the warm-up / capture forwards advanced the counters
-            # everything whose device address is baked into the captured kernel arguments stays referenced by the entry
-            st["keepalive"], st["gen"] = (prepared, tr._workspace, tr._native), tr._native_gen
             lat.copy_(saved)
         for i in range(len(timesteps)):
             st["sig"].copy_(sig_in[i:i + 1], non_blocking=True)
@@ -468,6 +467,15 @@ class QwenImagePipeline(nn.Module):
         """Run requests; samples that share (height, width, steps, cfg on/off, cfg scale) are step-batched, up to
         `od_config.max_step_batch` per DiT forward.  A request with several prompts / num_outputs_per_prompt > 1 returns
         its samples stacked along dim 0."""
+        from ...lora import normalize_combo
+
+        combos = {normalize_combo(getattr(r, "lora", None), getattr(r, "lora_scale", 1.0)) for r in requests}
+        if len(combos) > 1:
+            raise NotImplementedError("requests of one generate() call must name the same LoRA adapter combination (got "
+                                      f"{sorted(combos)}): the static path runs them in shared forwards; the step batcher serves "
+                                      "different adapters side by side")
+        if requests:
+            self.activate_lora(next(iter(combos)))
         samples = [s for i, r in enumerate(requests) for s in self.resolve_request(r, i)]
         groups: dict[tuple, list[int]] = {}
         for j, sm in enumerate(samples):
@@ -513,6 +521,38 @@ class QwenImagePipeline(nn.Module):
                 images[i] = dec[o:o + n]
                 o += n
         return [DiffusionOutput(output=images[i] if want[i] else lats[i]) for i in range(len(requests))]
+
+    # ---- LoRA adapters (diffusion/lora.py; merged on the device into copies of the targeted matrices, qwen_image_transformer.py)
+    def add_lora(self, name: str, path, target_modules=None) -> None:
+        self.transformer.load_lora_adapter(name, path, target_modules=target_modules)
+
+    def remove_lora(self, name: str) -> None:
+        """Forget `name` and free its merged sets.  A combination stays active after its last forward (the next forward states
+        its own), so an adapter that is merely still active is no obstacle: the base model is put back first.  Whether a LIVE
+        sample still names it is the caller's to know (the worker asks its step batcher: gpu_worker.WorkerProc)."""
+        if name not in self.lora_names():
+            raise KeyError(f"LoRA adapter {name!r} is not loaded")
+        if any(n == name for n, _ in self.transformer.active_lora):
+            self.activate_lora(())
+        self.transformer.delete_lora_adapter(name)
+        self._retire_graphs()
+
+    def lora_names(self) -> set:
+        return set(getattr(self.transformer, "_lora_adapters", ()))
+
+    def lora_resident(self, combo) -> bool:
+        """Would a forward under this combination run without a merge pass?"""
+        tr = self.transformer
+        return not combo or tuple(combo) == tr.active_lora or (tuple(combo), tr._weights_gen) in tr._lora_sets
+
+    def activate_lora(self, combo) -> None:
+        """Make `combo` (((name, weight), ...); () = the base model) the transformer's active combination."""
+        tr = self.transformer
+        if hasattr(tr, "set_lora_adapters"):
+            tr.set_lora_adapters(list(combo or ()))
+            self._retire_graphs()      # a switch that evicted a merged set: its graphs go now, before the new set is allocated
+        elif combo:
+            raise NotImplementedError(f"{type(tr).__name__} takes no LoRA adapters")
 
     DECODE_BATCH = 8                                                 # latents per VAE call (activations: 1 GB per latent at 1024^2)
 
@@ -846,7 +886,7 @@ class QwenImagePipeline(nn.Module):
             self._serve_step_body(st)
             return
         tr._native_weights()
-        if st["graph"] is None or st["gen"] != tr._native_gen:
+        if self._captured(st) is None:
             # warm-up on a side stream, then capture (see _denoise); both advance `lat` and the TeaCache state of the resident
             # samples, so those are saved and restored around them
             saved_lat, saved_idx = st["lat"].clone(), st["step_idx"].clone()
@@ -861,8 +901,7 @@ class QwenImagePipeline(nn.Module):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 self._serve_step_body(st)
-            st["graph"], st["gen"] = g, tr._native_gen
-            st["keepalive"] = (st["prepared"], tr._workspace, tr._native)
+            self._keep_captured(st, g, st["prepared"])
             st["lat"].copy_(saved_lat)
             if st.get("ragged"):
                 self._refresh_lat_in(st)                     # the warm-up / capture steps advanced the input rows as well
@@ -871,6 +910,37 @@ class QwenImagePipeline(nn.Module):
                 for i, sv in enumerate(saved_tc):
                     st["tc"].import_item(i, sv)
         st["graph"].replay()
+
+    # A state (static buffers of one batch composition) holds one captured graph PER pointer-table generation that is still live
+    # (`transformer.live_native_gens()`: the base table and one per resident LoRA set), so alternating between resident
+    # combinations replays and never re-captures.  A graph keeps the table it was captured under alive, merged weight copies
+    # included; graphs of a generation that is gone are therefore released in EVERY state, used again or not, as soon as the set
+    # of live generations changes - what bounds the merged copies on the device is `max_resident_loras`, not the graph caches.
+    def _retire_graphs(self, *more) -> None:
+        live = self.transformer.live_native_gens()
+        if live == self._graph_gens:
+            return
+        self._graph_gens = live
+        for s in [*more, *self._step_state.values(), *self._serve_states.values()]:
+            graphs = s.setdefault("graphs", {})
+            for g in [g for g in graphs if g not in live]:
+                del graphs[g]
+            if s.get("gen") not in graphs:
+                s["graph"] = s["gen"] = None
+
+    def _captured(self, st: dict):
+        """The graph of `st` captured under the transformer's CURRENT pointer table (None: capture one); `st["graph"]` names it."""
+        self._retire_graphs(st)
+        gen = self.transformer._native_gen
+        hit = st.setdefault("graphs", {}).get(gen)
+        st["graph"], st["gen"] = (hit[0], gen) if hit is not None else (None, None)
+        return st["graph"]
+
+    def _keep_captured(self, st: dict, graph, prepared) -> None:
+        """Everything whose device address is baked into the captured kernel arguments stays referenced next to the graph."""
+        tr = self.transformer
+        st["graphs"][tr._native_gen] = (graph, (prepared, tr._workspace, tr._native))
+        st["graph"], st["gen"] = graph, tr._native_gen
 
     def sample_result(self, a) -> torch.Tensor:
         """Final latents of a finished sample; its slot is released."""

@@ -21,9 +21,11 @@ import torch
 import torch.nn as nn
 
 import weakref
+from collections import OrderedDict
 
 from ...batch import RaggedBatch, build_ragged_batch
 from ...layers.adalayernorm import AdaLayerNorm
+from ... import lora
 from .... import _native as N
 from .... import ops
 from .rope import grid_tokens, normalize_grids, rope_table, rope_table_multi
@@ -45,6 +47,12 @@ class _Param(nn.Module):
         self.weight = nn.Parameter(torch.empty(shape, device=device, dtype=dtype), requires_grad=False)
         self.bias = nn.Parameter(torch.empty(out_features, device=device, dtype=dtype), requires_grad=False) if bias else None
         self.blockable = blockable
+        self._lora_owner = None      # (weakref to the model, module name) once the model registered this linear as a LoRA target
+
+    def active_weight(self) -> torch.Tensor:
+        """The matrix a forward reads: the parameter, or its merged copy while the model has a LoRA combination active."""
+        model = self._lora_owner[0]() if self._lora_owner is not None else None
+        return self.weight if model is None else model._active_tensor(self._lora_owner[1], self.weight)
 
     def forward(self, x: torch.Tensor, act_in: int = 0, act_out: int = 0) -> torch.Tensor:
         if self.weight.dim() != 2:
@@ -52,12 +60,13 @@ class _Param(nn.Module):
         if self.blockable:
             raise NotImplementedError("this projection lives inside the fused block kernels: call the block's forward")
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        w = self.active_weight()
         if x2.shape[0] <= 8 and x2.shape[1] <= 4096:            # conditioning vectors: weight-streaming GEMV
-            y = ops.linear_smallbatch(x2, self.weight, self.bias, act_in=act_in, act_out=act_out)
+            y = ops.linear_smallbatch(x2, w, self.bias, act_in=act_in, act_out=act_out)
         else:
             if act_in or act_out:
                 raise NotImplementedError("activations are fused only on the small-batch path")
-            y = ops.linear(x2, self.weight, self.bias)
+            y = ops.linear(x2, w, self.bias)
         return y.view(*x.shape[:-1], self.weight.shape[0])
 
 
@@ -332,7 +341,10 @@ class QwenImageTransformer2DModel(nn.Module):
             blk.layer_idx, blk._model_ref = i, weakref.ref(self)
         self.teacache = None         # TeaCacheConfig when the native TeaCache path is enabled (cache/teacache/backend.py)
         self._native = None        # (DitWeights struct, keep-alive list)
-        self._native_gen = 0       # bumped whenever the pointer table is invalidated (captured hipGraphs must be re-captured)
+        self._native_gen = 0       # names the storages the current pointer table reads: a fresh number whenever they change
+        self._gen_last = 0         # (captured hipGraphs are keyed by it); never reused
+        self._tables: dict = {}    # active LoRA combination (() = base) -> (generation, DitWeights, keep-alive) of every table
+                                   # whose storages still exist: going back to one is no new generation
         self._w_blocked = False    # the 8 big matrices per layer currently hold the K32-blocked re-layout
         self.fp8 = False           # enable_fp8(): the block GEMMs run on e4m3 copies of their weights (BASELINE config 5)
         self._fp8_classes = frozenset()
@@ -341,6 +353,17 @@ class QwenImageTransformer2DModel(nn.Module):
         self._sage_ws = None                # the sequence-parallel path's int8 attention workspace
         self._batch_cache: dict = {}
         self._mod_tables: dict = {}   # modulation_table_for_schedule(): (weights generation, sigmas, t_cond) -> table, newest last
+        # ---- LoRA (diffusion/lora.py): the parameters always hold the BASE weights; an active combination lives in merged COPIES
+        # of the targeted matrices, whose addresses the pointer table takes instead of the parameters'
+        self.max_resident_loras = max(1, int(getattr(od_config, "max_resident_loras", 1) or 1))
+        self._lora_targets = lora.target_shapes(num_layers, D, joint_attention_dim, in_channels, self.proj_out.weight.shape[0])
+        self._lora_adapters: dict = {}        # name -> lora.LoraAdapter
+        self._lora_active: tuple = ()         # ((name, weight), ...): the active combination; () = the base model
+        self._lora_sets: OrderedDict = OrderedDict()   # (combination, base-weights generation) -> {module: merged tensor}, LRU
+        self._weights_gen = 0                 # moves when the BASE weights (values or layout) change: every merged set is stale
+        mods = dict(self.named_modules())
+        for name in self._lora_targets:
+            mods[name]._lora_owner = (weakref.ref(self), name)
 
     # ------------------------------------------------------------------ weights
     @property
@@ -355,12 +378,134 @@ class QwenImageTransformer2DModel(nn.Module):
                         blk.img_mlp.net[0].proj.weight, blk.img_mlp.net[2].weight,
                         blk.txt_mlp.net[0].proj.weight, blk.txt_mlp.net[2].weight)
 
-    def _invalidate_native(self) -> None:
+    def _invalidate_native(self, base_changed: bool = True) -> None:
         """Drop the cached raw-pointer table.  The generation counter moves NOW (not when the table is lazily rebuilt), so
         that anything holding device addresses of the old storages — a captured hipGraph in the pipeline — is seen as stale
-        before it can be replayed."""
+        before it can be replayed.  `base_changed` (everything but a switch of the active LoRA combination): the base weights
+        moved or changed, so every merged LoRA set and every kept table is dropped as well; the active one is rebuilt lazily.
+        A switch to a combination whose table is still kept (its merged set is resident, the base weights did not move) takes
+        that table and ITS generation back: the graphs and modulation tables made under it are valid again, and those of
+        every other live table stay (`live_native_gens`)."""
+        if base_changed:
+            self._tables.clear()
+            if hasattr(self, "_lora_sets"):
+                self._lora_sets.clear()
+                self._weights_gen += 1
+        kept = self._tables.get(getattr(self, "_lora_active", ()))
+        if kept is not None:
+            self._native_gen, self._native = kept[0], kept[1:]
+            return
         self._native = None
-        self._native_gen += 1
+        self._gen_last += 1
+        self._native_gen = self._gen_last
+
+    def live_native_gens(self) -> set:
+        """The generations whose storages exist: the current one and those of the kept tables.  Whatever was captured or
+        cached under another generation (a hipGraph and what it keeps alive, a modulation table) is to be released."""
+        return {t[0] for t in self._tables.values()} | {self._native_gen}
+
+    # ------------------------------------------------------------------ LoRA adapters
+    @property
+    def active_lora(self) -> tuple:
+        """((name, weight), ...) of the active adapter combination; () = the base model."""
+        return self._lora_active
+
+    @property
+    def lora_targets(self) -> dict:
+        """{module name: (rows, columns, one of the eight K32-blocked GEMM matrices?)} of every matrix an adapter may target."""
+        return dict(self._lora_targets)
+
+    def load_lora_adapter(self, name: str, source, *, target_modules=None) -> None:
+        """Parse an adapter (a .safetensors / .pt / .bin path or a dict of tensors; key spellings: diffusion/lora.py) and keep
+        it under `name` on the host side of this model.  Nothing is merged until `set_lora_adapters` activates it.  Loading
+        under a name that exists replaces that adapter (a combination that uses it is re-merged)."""
+        ad = lora.parse_adapter(name, lora.read_adapter(source), self._lora_targets, self.inner_dim, target_modules)
+        dev = self.device
+        ad.updates = {k: (u.to(dev), d.to(dev), s) for k, (u, d, s) in ad.updates.items()}    # (_apply moves them with the model)
+        self._drop_lora_sets(name)
+        self._lora_adapters[name] = ad
+
+    def delete_lora_adapter(self, name: str) -> None:
+        if name not in self._lora_adapters:
+            raise KeyError(f"LoRA adapter {name!r} is not loaded")
+        if any(n == name for n, _ in self._lora_active):
+            raise ValueError(f"LoRA adapter {name!r} is active: deactivate it first (set_lora_adapters([]))")
+        self._drop_lora_sets(name)
+        del self._lora_adapters[name]
+
+    def _drop_lora_sets(self, name: str) -> None:
+        stale = [k for k in self._lora_sets if any(n == name for n, _ in k[0])]
+        for k in stale:
+            del self._lora_sets[k]
+            self._tables.pop(k[0], None)
+        if stale and any(n == name for n, _ in self._lora_active):
+            self._invalidate_native(base_changed=False)
+
+    def set_lora_adapters(self, names, weights=None) -> None:
+        """Activate a combination: `names` = adapter names (or (name, weight) pairs), `weights` = one factor per name (default
+        1).  [] / None = the base model: the pointer table goes back to the parameters themselves, so outputs are bit-equal to a
+        model that never saw an adapter.  Several adapters are stacked into ONE update per matrix (lora.stack).  The merge runs
+        lazily, when the pointer table is next built; a combination still resident (`max_resident_loras`, LRU) costs no launch."""
+        names = list(names or [])
+        if weights is not None:
+            if len(weights) != len(names):
+                raise ValueError(f"{len(weights)} weights for {len(names)} LoRA adapters")
+            names = list(zip(names, weights))
+        combo = lora.normalize_combo([(n, 1.0) if isinstance(n, str) else n for n in names])
+        for n, _ in combo:
+            if n not in self._lora_adapters:
+                raise KeyError(f"LoRA adapter {n!r} is not loaded")
+        if len({n for n, _ in combo}) != len(combo):
+            raise ValueError(f"LoRA combination {combo} names an adapter twice")
+        if combo != self._lora_active:
+            key = (combo, self._weights_gen)
+            if key in self._lora_sets:
+                self._lora_sets.move_to_end(key)
+            elif combo:
+                # not resident: make room NOW, before the new set is allocated, so that at most `max_resident_loras` sets
+                # exist at any time; the evicted tables' generations leave `live_native_gens`, which releases their graphs
+                while len(self._lora_sets) >= self.max_resident_loras:
+                    old, _ = self._lora_sets.popitem(last=False)
+                    self._tables.pop(old[0], None)
+            self._lora_active = combo
+            self._invalidate_native(base_changed=False)       # a new generation, or a kept table's own
+
+    def _merged_set(self) -> dict:
+        """{module: merged tensor} of the active combination, built by `ops.lora_merge` when not resident.  Built in the layout
+        the native runner reads (the eight GEMM matrices K32-blocked), from the base parameters, which are never written."""
+        if not self._lora_active:
+            return {}
+        self._set_weight_layout(True)
+        key = (self._lora_active, self._weights_gen)
+        hit = self._lora_sets.get(key)
+        if hit is not None:
+            self._lora_sets.move_to_end(key)
+            return hit
+        plan = lora.stack([(self._lora_adapters[n], w) for n, w in self._lora_active])
+        params = dict(self.named_parameters())
+        per_module: dict = {}
+        for (module, row0, rows), upd in plan.items():
+            per_module.setdefault(module, []).append((row0, rows, upd))
+        merged = {}
+        for module, ranges in per_module.items():
+            base = params[module + ".weight"].data
+            covered = sum(r for _, r, _ in ranges) == base.shape[0]
+            out = torch.empty_like(base) if covered else base.clone()        # rows outside every range keep the base values
+            for row0, rows, (up, down, scale) in ranges:
+                ops.lora_merge(base, out, up.to(base.device), down.to(base.device), scale, row0=row0, rows=rows,
+                               k32_blocked=self._lora_targets[module][2] and self._w_blocked)
+            merged[module] = out
+        self._lora_sets[key] = merged
+        while len(self._lora_sets) > self.max_resident_loras:
+            old, _ = self._lora_sets.popitem(last=False)
+            self._tables.pop(old[0], None)
+        return merged
+
+    def _active_tensor(self, module: str, param) -> torch.Tensor:
+        """The tensor a kernel reads for `module`'s weight: its merged copy under the active combination, else the parameter."""
+        if not self._lora_active:
+            return param.data
+        return self._merged_set().get(module, param.data)
 
     FP8_CLASSES = ("qkv", "out", "mlp_up", "mlp_down")      # the four GEMM classes of a block (both streams each)
 
@@ -426,7 +571,11 @@ class QwenImageTransformer2DModel(nn.Module):
         self._invalidate_native()
         self._workspace = None
         self._batch_cache.clear()
-        return super()._apply(fn, *args, **kwargs)
+        out = super()._apply(fn, *args, **kwargs)
+        dev = self.device
+        for ad in getattr(self, "_lora_adapters", {}).values():      # the adapter factors live where the weights live
+            ad.updates = {k: (u.to(dev), d.to(dev), s) for k, (u, d, s) in ad.updates.items()}
+        return out
 
     def init_random_(self, seed: int = 1234, std: float = 0.02) -> "QwenImageTransformer2DModel":
         """Synthetic weights ON DEVICE (bench only): >=2-D ~ N(0, std^2), biases 0, norm weights 1."""
@@ -480,22 +629,27 @@ class QwenImageTransformer2DModel(nn.Module):
         for n, p in self.named_parameters():
             if not p.is_cuda or p.dtype != BF16 or not p.is_contiguous():
                 raise N.OmniNativeError(f"parameter {n} must be a contiguous bf16 GPU tensor (got {p.device}, {p.dtype})")
+        merged = self._merged_set()                    # {} without an active LoRA combination: every pointer is a parameter's
+
+        def W(lin):                                    # the ACTIVE tensor of a linear's matrix (merged copy, else the parameter)
+            return lin.weight.data if not merged else merged.get(lin._lora_owner[1], lin.weight.data)
+
         L = len(self.transformer_blocks)
         layers = (N.DitLayerWeights * L)()
         for i, blk in enumerate(self.transformer_blocks):
             a = blk.attn
             vals = dict(
-                img_mod_w=blk.img_mod[1].weight, img_mod_b=blk.img_mod[1].bias,
-                txt_mod_w=blk.txt_mod[1].weight, txt_mod_b=blk.txt_mod[1].bias,
-                to_qkv_w=a.to_qkv.weight, to_qkv_b=a.to_qkv.bias, add_qkv_w=a.add_kv_proj.weight,
+                img_mod_w=W(blk.img_mod[1]), img_mod_b=blk.img_mod[1].bias,
+                txt_mod_w=W(blk.txt_mod[1]), txt_mod_b=blk.txt_mod[1].bias,
+                to_qkv_w=W(a.to_qkv), to_qkv_b=a.to_qkv.bias, add_qkv_w=W(a.add_kv_proj),
                 add_qkv_b=a.add_kv_proj.bias, norm_q_w=a.norm_q.weight, norm_k_w=a.norm_k.weight,
                 norm_added_q_w=a.norm_added_q.weight, norm_added_k_w=a.norm_added_k.weight,
-                to_out_w=a.to_out[0].weight, to_out_b=a.to_out[0].bias, to_add_out_w=a.to_add_out.weight,
+                to_out_w=W(a.to_out[0]), to_out_b=a.to_out[0].bias, to_add_out_w=W(a.to_add_out),
                 to_add_out_b=a.to_add_out.bias,
-                img_mlp_w1=blk.img_mlp.net[0].proj.weight, img_mlp_b1=blk.img_mlp.net[0].proj.bias,
-                img_mlp_w2=blk.img_mlp.net[2].weight, img_mlp_b2=blk.img_mlp.net[2].bias,
-                txt_mlp_w1=blk.txt_mlp.net[0].proj.weight, txt_mlp_b1=blk.txt_mlp.net[0].proj.bias,
-                txt_mlp_w2=blk.txt_mlp.net[2].weight, txt_mlp_b2=blk.txt_mlp.net[2].bias)
+                img_mlp_w1=W(blk.img_mlp.net[0].proj), img_mlp_b1=blk.img_mlp.net[0].proj.bias,
+                img_mlp_w2=W(blk.img_mlp.net[2]), img_mlp_b2=blk.img_mlp.net[2].bias,
+                txt_mlp_w1=W(blk.txt_mlp.net[0].proj), txt_mlp_b1=blk.txt_mlp.net[0].proj.bias,
+                txt_mlp_w2=W(blk.txt_mlp.net[2]), txt_mlp_b2=blk.txt_mlp.net[2].bias)
             for k, v in vals.items():
                 setattr(layers[i], k, v.data_ptr())
         w = N.DitWeights()
@@ -504,34 +658,35 @@ class QwenImageTransformer2DModel(nn.Module):
         w.out_channels_packed = self.proj_out.weight.shape[0]
         w.gemm_w_k32_blocked = 1 if self._w_blocked else 0
         te = self.time_text_embed.timestep_embedder
-        w.t_lin1_w, w.t_lin1_b = te.linear_1.weight.data_ptr(), te.linear_1.bias.data_ptr()
-        w.t_lin2_w, w.t_lin2_b = te.linear_2.weight.data_ptr(), te.linear_2.bias.data_ptr()
+        w.t_lin1_w, w.t_lin1_b = W(te.linear_1).data_ptr(), te.linear_1.bias.data_ptr()
+        w.t_lin2_w, w.t_lin2_b = W(te.linear_2).data_ptr(), te.linear_2.bias.data_ptr()
         w.txt_norm_w = self.txt_norm.weight.data_ptr()
-        w.img_in_w, w.img_in_b = self.img_in.weight.data_ptr(), self.img_in.bias.data_ptr()
-        w.txt_in_w, w.txt_in_b = self.txt_in.weight.data_ptr(), self.txt_in.bias.data_ptr()
-        w.norm_out_w, w.norm_out_b = self.norm_out.linear.weight.data_ptr(), self.norm_out.linear.bias.data_ptr()
-        w.proj_out_w, w.proj_out_b = self.proj_out.weight.data_ptr(), self.proj_out.bias.data_ptr()
+        w.img_in_w, w.img_in_b = W(self.img_in).data_ptr(), self.img_in.bias.data_ptr()
+        w.txt_in_w, w.txt_in_b = W(self.txt_in).data_ptr(), self.txt_in.bias.data_ptr()
+        w.norm_out_w, w.norm_out_b = W(self.norm_out.linear).data_ptr(), self.norm_out.linear.bias.data_ptr()
+        w.proj_out_w, w.proj_out_b = W(self.proj_out).data_ptr(), self.proj_out.bias.data_ptr()
         w.layers = C.cast(layers, C.POINTER(N.DitLayerWeights))
-        keep = [layers]
+        keep = [layers, merged]      # the merged copies stay alive as long as anything (a captured hipGraph) holds this table
         if self.fp8:
             f8 = (N.DitFp8Layer * L)()
             names = N._FP8_FIELDS
             for i, blk in enumerate(self.transformer_blocks):
                 a = blk.attn
-                mats = (a.to_qkv.weight, a.add_kv_proj.weight, a.to_out[0].weight, a.to_add_out.weight,
-                        blk.img_mlp.net[0].proj.weight, blk.img_mlp.net[2].weight,
-                        blk.txt_mlp.net[0].proj.weight, blk.txt_mlp.net[2].weight)
+                mats = (W(a.to_qkv), W(a.add_kv_proj), W(a.to_out[0]), W(a.to_add_out),
+                        W(blk.img_mlp.net[0].proj), W(blk.img_mlp.net[2]),
+                        W(blk.txt_mlp.net[0].proj), W(blk.txt_mlp.net[2]))       # the ACTIVE tensors: e4m3 copies follow the adapter
                 cls_of = ("qkv", "qkv", "out", "out", "mlp_up", "mlp_down", "mlp_up", "mlp_down")
                 for f, m, c in zip(names, mats, cls_of):
                     if c not in self._fp8_classes:
                         continue                                                              # NULL pointers: class stays bf16
-                    w8, sc = ops.quantize_fp8_rows(m.data, x_k32_blocked=self._w_blocked)     # per output channel
+                    w8, sc = ops.quantize_fp8_rows(m, x_k32_blocked=self._w_blocked)     # per output channel
                     keep += [w8, sc]
                     setattr(f8[i], f + ("_w8" if "mlp" not in f else "_8"), w8.data_ptr())
                     setattr(f8[i], f + "_s", sc.data_ptr())
             w.fp8_layers = C.cast(f8, C.POINTER(N.DitFp8Layer))
             keep.append(f8)
         self._native = (w, keep)
+        self._tables[self._lora_active] = (self._native_gen, w, keep)
         return w
 
     # ------------------------------------------------------------------ batches
@@ -668,7 +823,8 @@ class QwenImageTransformer2DModel(nn.Module):
         key = (self._native_gen, sig.numpy().tobytes(), None if additional_t_cond is None else tuple(int(t) for t in additional_t_cond))
         hit = self._mod_tables.pop(key, None)
         if hit is None:
-            for k in [k for k in self._mod_tables if k[0] != self._native_gen]:
+            live = self.live_native_gens()
+            for k in [k for k in self._mod_tables if k[0] not in live]:
                 del self._mod_tables[k]                          # tables of weights that no longer exist
             hit = self.modulation_table(sigma, additional_t_cond)
         self._mod_tables[key] = hit                              # newest last

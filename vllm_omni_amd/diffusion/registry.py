@@ -47,8 +47,11 @@ def apply_vae_memory_flags(model, od_config: OmniDiffusionConfig):
 def initialize_model(od_config: OmniDiffusionConfig, **kw):
     """Instantiate `od_config.model_class_name` with the registry contract `__init__(*, od_config, prefix="")`, then hand the
     VAE its memory flags."""
-    return apply_vae_memory_flags(resolve_model_cls(od_config.model_class_name or "QwenImagePipeline")(od_config=od_config, **kw),
-                                  od_config)
+    model = apply_vae_memory_flags(resolve_model_cls(od_config.model_class_name or "QwenImagePipeline")(od_config=od_config, **kw),
+                                   od_config)
+    for name, path in (getattr(od_config, "lora_adapters", None) or {}).items():      # NEW: preloaded LoRA adapters by name
+        model.add_lora(name, path)
+    return model
 
 
 def _load_process_func(od_config: OmniDiffusionConfig, table: dict[str, str]):

@@ -43,6 +43,9 @@ class OmniDiffusionRequest:
     cfg_normalize: bool | None = None                  # Layered: norm-rescaled true-CFG (reference default False)
     use_en_prompt: bool | None = None                  # Layered: caption language
     max_sequence_length: int | None = None
+    # ---- NEW (not in the reference): the LoRA adapter(s) this request runs under, by the names they were loaded with
+    lora: str | list[tuple[str, float]] | None = None  # one name, or [(name, weight), ...] stacked; None = the base model, always
+    lora_scale: float = 1.0                            # weight of the single-name form
 
     def __post_init__(self) -> None:
         if isinstance(self.prompt_embeds, (list, tuple)):          # reference type: list[Tensor] | Tensor, default []

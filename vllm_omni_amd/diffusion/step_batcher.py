@@ -27,6 +27,8 @@ class ActiveSample:
     n_steps: int = 0
     state: dict = field(default_factory=dict)      # per-sample schedule tensors (pipeline-owned)
     seq: int = 0                  # arrival order
+    lora: tuple = ()              # ((adapter name, weight), ...) of the request; () = the base model
+    last_tick: int = 0            # forward count when the sample arrived or last ran (LoRA switch patience)
 
 
 class ContinuousStepBatcher:
@@ -53,14 +55,25 @@ class ContinuousStepBatcher:
         self._inflight: collections.deque = collections.deque()        # (start event, end event, samples in the step)
         # serving statistics (bench.py's per-worker busy fraction): device seconds inside steps vs the span they cover
         self._stats = {"steps": 0, "sample_steps": 0, "busy_s": 0.0, "first": None, "last": None}
+        # LoRA: forwards a sample of a non-resident adapter combination waits while resident combinations have work
+        self.lora_switch_patience = max(0, int(getattr(cfg, "lora_switch_patience", 8)))
 
     # ------------------------------------------------------------------ admission
     def add(self, req, tag) -> None:
         """Validate + expand the request now (errors surface at admission, not in the middle of someone else's step)."""
+        from .lora import normalize_combo
+
+        combo = normalize_combo(getattr(req, "lora", None), getattr(req, "lora_scale", 1.0))
+        if combo:
+            names = getattr(self.pipeline, "lora_names", None)
+            known = names() if names is not None else ()
+            for n, _ in combo:
+                if n not in known:
+                    raise KeyError(f"LoRA adapter {n!r} is not loaded (known: {sorted(known)})")
         samples = self.pipeline.resolve_request(req)
         self._pending[tag] = {"req": req, "left": len(samples), "done": {}, "n": len(samples)}
         for sm in samples:
-            a = ActiveSample(tag=tag, sample=sm, seq=next(self._seq))
+            a = ActiveSample(tag=tag, sample=sm, seq=next(self._seq), lora=combo, last_tick=self._tick)
             self.pipeline.begin_sample(a)
             self.active.append(a)
 
@@ -126,13 +139,27 @@ class ContinuousStepBatcher:
         admitted, so a request larger than the budget still runs (alone).  A key that can mix sizes (the pipeline's
         `mixed_step_batch`) hands its group over LONGEST ITEM FIRST, stable by arrival: within every head's range of the
         attention grid the long items' blocks are issued first, and the pipeline's per-composition state is keyed by the ordered sizes, so one
-        multiset of sizes maps to one state."""
+        multiset of sizes maps to one state.
+
+        LoRA: the adapter combination of a request joins the batch key in every mode, so two samples under different adapters never
+        share a forward (a request without one keeps the key it always had).  Round-robin over keys would then pay a merge pass
+        per forward whenever two adapters are live, so keys whose combination is RESIDENT (the base model, the active
+        combination, a merged set still kept: `pipeline.lora_resident`) go first; a key with a non-resident combination is
+        served once its oldest sample has waited `lora_switch_patience` forwards, and at once when no resident key has work."""
         by_key: dict[Any, list[ActiveSample]] = {}
         for a in sorted(self.active, key=lambda a: a.seq):
-            by_key.setdefault(self.pipeline.batch_key(a), []).append(a)
+            k = self.pipeline.batch_key(a)
+            by_key.setdefault((k, a.lora) if a.lora else k, []).append(a)
         for k in [k for k in self._last_served if k not in by_key]:
             del self._last_served[k]
-        key = min(by_key, key=lambda k: (self._last_served.get(k, -1), by_key[k][0].seq))
+        eligible = list(by_key)
+        if any(v[0].lora for v in by_key.values()):
+            resident = getattr(self.pipeline, "lora_resident", None)
+            is_res = {k: (not v[0].lora) or resident is None or bool(resident(v[0].lora)) for k, v in by_key.items()}
+            if any(is_res.values()):
+                eligible = [k for k, v in by_key.items()
+                            if is_res[k] or self._tick - v[0].last_tick >= self.lora_switch_patience]
+        key = min(eligible, key=lambda k: (self._last_served.get(k, -1), by_key[k][0].seq))
         self._tick += 1
         self._last_served[key] = self._tick
         if self.max_tokens is None:
@@ -147,6 +174,8 @@ class ContinuousStepBatcher:
                 used += t
         if all(a.sample.get("lat") is not None for a in group) and len({self._total_rows(a) for a in group}) > 1:
             group = sorted(group, key=lambda a: (-self._total_rows(a), a.seq))
+        for a in group:
+            a.last_tick = self._tick
         return group
 
     @staticmethod
@@ -182,6 +211,9 @@ class ContinuousStepBatcher:
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
         try:
+            activate = getattr(self.pipeline, "activate_lora", None)
+            if activate is not None:                        # every forward states its combination: () puts the base model back
+                activate(group[0].lora)
             self.pipeline.denoise_one_step(group)
         except Exception as e:  # noqa: BLE001 — a failing step aborts the REQUESTS that were in it, nothing else
             return self.abort({a.tag for a in group}, f"{type(e).__name__}: {e}")

@@ -102,6 +102,12 @@ class GPUWorker:
                 self.pipeline._req_params(r)
                 if self.world > 1 and ((r.num_outputs_per_prompt or 1) != 1 or (isinstance(r.prompt, list) and len(r.prompt) != 1)):
                     raise NotImplementedError("a data-parallel batch carries one sample per request (one gather row each)")
+            from ..lora import normalize_combo
+
+            combos = {normalize_combo(getattr(r, "lora", None), getattr(r, "lora_scale", 1.0)) for r in reqs}
+            if len(combos) > 1:
+                raise NotImplementedError("requests of one execute_model() call must name the same LoRA adapter combination "
+                                          f"(got {sorted(combos)}); the step batcher serves different adapters side by side")
             pl = self.pipeline
             # gather key of a request: (height, width, packed-latent rows per sample, images per sample).  The text-to-image
             # and Edit pipelines finish with (h/16)(w/16) rows and one image; the Layered pipeline with (layers + 1) frames of
@@ -298,6 +304,8 @@ class WorkerProc:
             try:
                 if msg["method"] == "serving_stats":        # this process's step batcher (bench.py: per-worker busy fraction)
                     fn = self.batcher.stats
+                elif msg["method"] in ("add_lora", "remove_lora", "lora_in_use"):   # they ask the batcher about live samples
+                    fn = getattr(self, msg["method"])
                 else:
                     fn = getattr(self.worker, msg["method"], None) or getattr(self.worker.pipeline, msg["method"])
                 res = fn(*msg.get("args", ()), **msg.get("kwargs", {}))
@@ -309,6 +317,26 @@ class WorkerProc:
         else:
             self.outbox.put({"type": "error", "rank": self.rank, "error": f"unknown message type {kind!r}"})
         return True
+
+    # -- LoRA adapters: the pipeline holds them, the step batcher knows which live samples name them ----------------------------
+    def lora_in_use(self, name: str) -> int:
+        """Live samples of this worker whose adapter combination names `name`."""
+        return sum(1 for a in self.batcher.active if any(n == name for n, _ in (a.lora or ())))
+
+    def add_lora(self, name: str, path, target_modules=None) -> None:
+        self._refuse_lora_in_use(name, "replaced")
+        self.worker.pipeline.add_lora(name, path, target_modules=target_modules)
+
+    def remove_lora(self, name: str) -> None:
+        """An adapter that is merely still ACTIVE (a combination stays active after its last forward) is deactivated by the
+        pipeline; one that samples in flight still name is refused: their remaining steps need it."""
+        self._refuse_lora_in_use(name, "removed")
+        self.worker.pipeline.remove_lora(name)
+
+    def _refuse_lora_in_use(self, name: str, what: str) -> None:
+        n = self.lora_in_use(name)
+        if n:
+            raise ValueError(f"LoRA adapter {name!r} cannot be {what}: {n} sample(s) in flight use it")
 
     POLL_S = 0.001        # inbox wait while the device is busy (throttled) or results are in flight
 

@@ -108,6 +108,13 @@ class AsyncOmniDiffusion:
         """Diffusion has no token stream: one result when the image is done (reference :208-229)."""
         yield await self.generate(prompt=prompt, request_id=request_id, **kwargs)
 
+    def add_lora(self, name: str, path: str) -> None:
+        """Load a LoRA adapter under `name` on every worker (DiffusionEngine.add_lora)."""
+        self.engine.add_lora(name, path)
+
+    def remove_lora(self, name: str) -> None:
+        self.engine.remove_lora(name)
+
     def close(self) -> None:
         if self._closed:
             return

@@ -434,6 +434,34 @@ def cfg_euler_step_ragged_(latents, pred, lat_in, reqs, n_reqs: int, total_rows:
     return latents
 
 
+def lora_merge(w_base, w_out, up, down, scale: float, *, row0: int = 0, rows: int | None = None, k32_blocked: bool = False):
+    """omni_lora_merge: w_out[n] = bf16(w_base[n] + scale * up[n - row0] @ down) for n in [row0, row0 + rows), fp32 accumulate,
+    one rounding; other rows of w_out are not touched.  w_base / w_out [N, K] bf16 (the same tensor = in place), row-major
+    (a row stride is honoured) or, `k32_blocked`, holding the K32-blocked order of `w_to_k32_blocked`; up [rows, R] and down
+    [R, K] contiguous bf16, R <= 256.  Returns w_out."""
+    if not N.features() & N.FEATURE_LORA_MERGE:
+        raise N.OmniNativeError("this libomni_cdna4.so does not report OMNI_FEATURE_LORA_MERGE: it has no omni_lora_merge "
+                                "(the device-side merge of LoRA adapters); there is no torch fallback")
+    n, k, ldw = _rows2d(w_base, "w_base")
+    if tuple(w_out.shape) != (n, k) or w_out.dim() != 2 or w_out.stride(0) != ldw:
+        raise N.OmniNativeError(f"lora_merge: w_out must match w_base's shape and row stride ({n}, {k}; {ldw})")
+    if k32_blocked and not (w_base.is_contiguous() and w_out.is_contiguous()):
+        raise N.OmniNativeError("lora_merge: a K32-blocked matrix is one contiguous [K/32][N][32] buffer")
+    rows = n - row0 if rows is None else rows
+    if up.dim() != 2 or down.dim() != 2 or not up.is_contiguous() or not down.is_contiguous():
+        raise N.OmniNativeError("lora_merge: up [rows, R] and down [R, K] must be contiguous 2-D tensors")
+    if up.shape[0] != rows or up.shape[1] != down.shape[0] or down.shape[1] != k:
+        raise N.OmniNativeError(f"lora_merge: up {tuple(up.shape)} / down {tuple(down.shape)} do not fit rows {rows} of a "
+                                f"[{n}, {k}] matrix")
+    p = N.LoraMergeParams()
+    p.w_base, p.w_out = _p(w_base, name="w_base"), _p(w_out, name="w_out")
+    p.up, p.down = _p(up, name="up"), _p(down, name="down")
+    p.N, p.K, p.R, p.row0, p.rows = n, k, up.shape[1], row0, rows
+    p.w_k32_blocked, p.ldw, p.scale = (1 if k32_blocked else 0), ldw, float(scale)
+    N.check(N.lib().omni_lora_merge(C.byref(p), _stream()), "omni_lora_merge")
+    return w_out
+
+
 def vae_conv2d(x, w, bias=None, *, gamma=None, silu=True, res=None, upsample2x=False, downsample2x=False, clamp=None,
                out=None, x_bordered=False, y_bordered=False, norm_gamma=None, norm_silu=True, keep_raw=True):
     """NHWC bf16 conv (3x3 pad 1 or 1x1): x [B,H,W,Cin], w [Cout,ks,ks,Cin].  downsample2x: the encoder's zero-pad
