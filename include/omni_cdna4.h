@@ -55,6 +55,7 @@ const char* omni_status_string(int status);
                                          * the items of a batch with omni_dit_batch.teacache set may differ in image rows */
 #define OMNI_FEATURE_CFG_EULER_RAGGED 4u /* the library exports omni_cfg_euler_step_ragged: a function pointer, see there */
 #define OMNI_FEATURE_LORA_MERGE 8u /* the library exports omni_lora_merge: a function pointer, see there */
+#define OMNI_FEATURE_TEXT_ENCODER 16u /* the library exports omni_qwen2_text_forward and its companions: function pointers */
 uint32_t omni_features(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -487,6 +488,79 @@ typedef struct omni_lora_merge_params {
 } omni_lora_merge_params;
 /* a const function POINTER like omni_cfg_euler_step_ragged, for the same reason */
 extern int (*const omni_lora_merge)(const omni_lora_merge_params* p, omni_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Prompt encoder: the Qwen2.5-VL TEXT model (HF transformers `Qwen2_5_VLTextModel`, 28 decoder layers at hidden 3584 / 28 query
+ * heads over 4 K/V heads / intermediate 18944) as one native call (optional symbols of ABI v14: ask
+ * omni_features() & OMNI_FEATURE_TEXT_ENCODER).  Replaces the HF eager pass behind `_get_qwen_prompt_embeds`
+ * (vllm_omni/diffusion/models/qwen_image/pipeline_qwen_image.py:351-392) for prompts WITHOUT pictures: their three M-RoPE position
+ * rows are equal, so the rotary embedding is plain rotate-half RoPE at one position per token.
+ * Per layer: RMSNorm -> fused q|k|v GEMM (+ bias) -> RoPE on q, k -> causal attention with grouped K/V heads -> o_proj + residual
+ * -> RMSNorm -> fused gate|up GEMM -> silu(gate) * up -> down_proj + residual; after the last layer the final RMSNorm (HF's
+ * `hidden_states[-1]` is post-norm).  Runs over the PACKED valid tokens of all prompts: no pad rows.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct omni_text_layer_weights {
+  const omni_bf16* input_norm_w; /* [D] */
+  const omni_bf16* qkv_w;        /* [(H + 2 H_kv) * 128, D]: rows of q_proj | k_proj | v_proj */
+  const omni_bf16* qkv_b;        /* [(H + 2 H_kv) * 128] */
+  const omni_bf16* o_w;          /* [D, H * 128], no bias */
+  const omni_bf16* post_norm_w;  /* [D] */
+  const omni_bf16* gate_up_w;    /* [2 I, D]: rows of gate_proj | up_proj, no bias */
+  const omni_bf16* down_w;       /* [D, I], no bias */
+} omni_text_layer_weights;
+
+typedef struct omni_text_weights {
+  int32_t num_layers, hidden_size, num_heads, num_kv_heads, head_dim, intermediate_size, vocab_size;
+  int32_t gemm_w_k32_blocked;    /* 1: qkv_w, o_w, gate_up_w, down_w of every layer are stored K32-blocked
+                                  * (omni_gemm_params.w_k32_blocked); everything else is always row-major */
+  float rms_norm_eps;
+  int32_t rope_npos;             /* rows of the RoPE tables */
+  const omni_bf16* embed_tokens; /* [vocab_size, D] */
+  const omni_bf16* final_norm_w; /* [D] */
+  const omni_bf16* ones;         /* [D] bf16 1.0: the gate of the residual adds (OMNI_EPI_BIAS_GATE_RES with gate 1 is exact) */
+  const float* rope_cos;         /* [rope_npos, 64] fp32: cos(p * theta^(-i / 64)), built once on the host from rope_theta */
+  const float* rope_sin;
+  const omni_text_layer_weights* layers; /* HOST array [num_layers] of device pointers */
+} omni_text_weights;
+
+typedef struct omni_text_batch {
+  int32_t n_prompts, total_rows; /* prompts (<= 64) and the sum of their token counts */
+  int32_t max_seqlen;            /* at least the longest prompt's token count (sizes the attention grid) */
+  int32_t reserved;              /* 0 */
+  const int32_t* input_ids;      /* [total_rows] token ids, prompt after prompt */
+  const int32_t* cu_seqlens;     /* [n_prompts + 1] prefix sums of the token counts */
+  const int32_t* row_pos;        /* [total_rows] position of each token inside its prompt = RoPE table row */
+  omni_bf16* out;                /* [total_rows, D] the last hidden state (after the final norm) */
+  void* workspace;               /* DEVICE, 16-byte aligned, as many bytes as omni_qwen2_text_workspace_bytes answers for
+                                  * (w, total_rows); its first 256 bytes hold the error word below: ZERO them once when the
+                                  * buffer is allocated */
+  size_t workspace_bytes;
+} omni_text_batch;
+/* const function POINTERS like omni_lora_merge, for the same reason.
+ * omni_qwen2_text_forward: one call enqueues the whole forward on `stream`; no allocation.  Status before any launch: null
+ * pointer, non-positive count, short workspace -> OMNI_ERR_BAD_ARG; head_dim != 128, hidden_size or intermediate_size not a
+ * multiple of 64, hidden_size > 8192, num_heads % num_kv_heads != 0, more than 64 prompts -> OMNI_ERR_UNSUPPORTED.
+ * Device-side errors: a token id outside [0, vocab_size) yields a ZERO embedding row (never an out-of-range read), a position
+ * outside [0, rope_npos) is clamped; either sets the error word at the front of the workspace, which the NEXT call over the same
+ * workspace reads back (4 bytes, in front of its first launch: the one host read of a call), clears and reports as
+ * OMNI_ERR_BAD_ARG without running. */
+extern int (*const omni_qwen2_text_forward)(const omni_text_weights* w, const omni_text_batch* b, omni_stream stream);
+/* 0 for weights the forward refuses */
+extern size_t (*const omni_qwen2_text_workspace_bytes)(const omni_text_weights* w, int32_t total_rows);
+/* The three row kernels of the forward on their own (same feature bit).
+ * omni_text_rope_neox: rotate-half RoPE in place on the q and k blocks of qkv [rows, ld >= (H + 2 H_kv) * 128]; for pair
+ * (i, i + 64) of a head: out[i] = x[i] cos[p, i] - x[i + 64] sin[p, i]; out[i + 64] = x[i + 64] cos[p, i] + x[i] sin[p, i] with
+ * p = row_pos[row]; the v block is not touched.
+ * err (nullable DEVICE int32): set non-zero when a position had to be clamped into [0, npos). */
+extern int (*const omni_text_rope_neox)(omni_bf16* qkv, int64_t ld, int32_t rows, int32_t H, int32_t H_kv, const float* cos_tab,
+                                        const float* sin_tab, int32_t npos, const int32_t* row_pos, int32_t* err, omni_stream stream);
+/* omni_text_swiglu: y[r, j] = silu(gate_up[r, j]) * gate_up[r, I + j]; y row-major (ldy) or, y_k32_rows = R > 0, K32-blocked
+ * [I / 32][R][32] (omni_gemm_group.a_k32_rows of the GEMM that reads it; I % 32 == 0).  I % 8 == 0. */
+extern int (*const omni_text_swiglu)(const omni_bf16* gate_up, int64_t ldgu, omni_bf16* y, int64_t ldy, int32_t rows, int32_t I,
+                                     int32_t y_k32_rows, omni_stream stream);
+/* omni_text_embed_gather: h[r, :] = table[ids[r], :]; an id outside [0, vocab) writes zeros and sets *err (DEVICE int32) to 1. */
+extern int (*const omni_text_embed_gather)(const omni_bf16* table, int32_t vocab, int32_t D, const int32_t* ids, int32_t rows,
+                                           omni_bf16* h, int64_t ldh, int32_t* err, omni_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * VAE kernels (AutoencoderKLQwenImage.decode — and .encode for the Edit pipelines — for one frame,

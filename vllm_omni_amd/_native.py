@@ -100,6 +100,31 @@ class LoraMergeParams(C.Structure):
     ]
 
 
+class TextLayerWeights(C.Structure):
+    """omni_text_layer_weights: device pointers of one Qwen2.5-VL decoder layer (fused q|k|v and gate|up matrices)."""
+    _fields_ = [(n, c_bf16_p) for n in ("input_norm_w", "qkv_w", "qkv_b", "o_w", "post_norm_w", "gate_up_w", "down_w")]
+
+
+class TextWeights(C.Structure):
+    """omni_text_weights: geometry, embedding, RoPE tables and the HOST array of layers of omni_qwen2_text_forward."""
+    _fields_ = [
+        ("num_layers", C.c_int32), ("hidden_size", C.c_int32), ("num_heads", C.c_int32), ("num_kv_heads", C.c_int32),
+        ("head_dim", C.c_int32), ("intermediate_size", C.c_int32), ("vocab_size", C.c_int32), ("gemm_w_k32_blocked", C.c_int32),
+        ("rms_norm_eps", C.c_float), ("rope_npos", C.c_int32),
+        ("embed_tokens", c_bf16_p), ("final_norm_w", c_bf16_p), ("ones", c_bf16_p), ("rope_cos", c_f32_p), ("rope_sin", c_f32_p),
+        ("layers", C.POINTER(TextLayerWeights)),
+    ]
+
+
+class TextBatch(C.Structure):
+    """omni_text_batch: the packed tokens of up to 64 prompts, the output and the caller-owned workspace."""
+    _fields_ = [
+        ("n_prompts", C.c_int32), ("total_rows", C.c_int32), ("max_seqlen", C.c_int32), ("reserved", C.c_int32),
+        ("input_ids", c_i32_p), ("cu_seqlens", c_i32_p), ("row_pos", c_i32_p), ("out", c_bf16_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 class ConvParams(C.Structure):
     _fields_ = [
         ("x", c_bf16_p), ("w", c_bf16_p), ("bias", c_bf16_p), ("gamma", c_bf16_p), ("res", c_bf16_p), ("y", c_bf16_p),
@@ -247,6 +272,13 @@ FEATURE_PROTOTYPES = {
     "omni_cfg_euler_step_ragged": (C.c_int, [c_bf16_p, C.c_int32, c_bf16_p, C.c_int32, c_bf16_p, C.c_int32, C.c_void_p, C.c_int32,
                                              C.c_int32, C.c_int32, c_f32_p, C.c_int32, C.c_int32, C.c_void_p], 4),
     "omni_lora_merge": (C.c_int, [C.POINTER(LoraMergeParams), C.c_void_p], 8),
+    "omni_qwen2_text_forward": (C.c_int, [C.POINTER(TextWeights), C.POINTER(TextBatch), C.c_void_p], 16),
+    "omni_qwen2_text_workspace_bytes": (C.c_size_t, [C.POINTER(TextWeights), C.c_int32], 16),
+    "omni_text_rope_neox": (C.c_int, [c_bf16_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_f32_p, c_f32_p, C.c_int32, c_i32_p,
+                                      c_i32_p, C.c_void_p], 16),
+    "omni_text_swiglu": (C.c_int, [c_bf16_p, C.c_int64, c_bf16_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p], 16),
+    "omni_text_embed_gather": (C.c_int, [c_bf16_p, C.c_int32, C.c_int32, c_i32_p, C.c_int32, c_bf16_p, C.c_int64, c_i32_p,
+                                         C.c_void_p], 16),
 }
 
 # symbols a library of the SAME ABI version may lack: they were added together with a field that went into former struct
@@ -256,6 +288,7 @@ FEATURE_ATTN_F16 = 1                              # OMNI_FEATURE_ATTN_F16
 FEATURE_TEACACHE_RAGGED = 2                       # OMNI_FEATURE_TEACACHE_RAGGED
 FEATURE_CFG_EULER_RAGGED = 4                      # OMNI_FEATURE_CFG_EULER_RAGGED: omni_cfg_euler_step_ragged is exported
 FEATURE_LORA_MERGE = 8                            # OMNI_FEATURE_LORA_MERGE: omni_lora_merge is exported
+FEATURE_TEXT_ENCODER = 16                         # OMNI_FEATURE_TEXT_ENCODER: omni_qwen2_text_forward and its companions are exported
 ELEM_BF16, ELEM_F16 = 0, 1                        # omni_attn_params.elem_type
 
 _lib = None

@@ -151,6 +151,10 @@ class OmniDiffusionConfig:
                                      # a resident combination launches nothing
     lora_switch_patience: int = 8    # NEW: forwards the step batcher lets a sample of a NON-resident adapter combination wait
                                      # while resident combinations have work (a switch costs a pass over the targeted weights)
+    native_text_encoder: bool = False  # NEW, opt-in: `load_text_encoder` builds the Qwen2.5-VL prompt encoder on this library
+                                     # (NativeQwenPromptEncoder: all decoder layers in one omni_qwen2_text_forward over the packed
+                                     # tokens) instead of HF eager.  Text-to-image only: the Edit / Edit-Plus / Layered pipelines
+                                     # need the HF model's vision tower / caption path and refuse the flag at construction
     max_step_tokens: int | None = None  # NEW: admission bound next to max_step_batch — the largest sum of image rows x CFG
                                      # branches one forward may hold (the oldest sample always runs, alone if need be)
     # ---- the reference's remaining fields (data.py:255-360), so that a config written for it constructs here unchanged.

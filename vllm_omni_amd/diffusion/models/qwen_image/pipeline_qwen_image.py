@@ -61,7 +61,8 @@ class QwenImagePipeline(nn.Module):
             od_config=self.od_config, device=dev, **(transformer_kwargs or {}))
         self.vae = vae if vae is not None else AutoencoderKLQwenImage(device=dev)
         self.scheduler = FlowMatchEulerSchedule()
-        self.text_encoder = text_encoder      # QwenPromptEncoder (text_encoder.py) or None: requests then carry prompt_embeds
+        self.text_encoder = text_encoder      # QwenPromptEncoder / NativeQwenPromptEncoder (text_encoder.py), used as given, or
+                                              # None: requests then carry prompt_embeds
         self.vae_scale_factor = 8
         self.default_sample_size = 128
         self._latents_mean = torch.tensor(self.vae.config.latents_mean).view(1, -1, 1, 1, 1)
@@ -382,7 +383,7 @@ class QwenImagePipeline(nn.Module):
 
         from transformers import AutoTokenizer, Qwen2_5_VLForConditionalGeneration
 
-        from .text_encoder import QwenPromptEncoder
+        from .text_encoder import NativeQwenPromptEncoder, QwenPromptEncoder
 
         te_dir, tok_dir = os.path.join(model_dir, "text_encoder"), os.path.join(model_dir, "tokenizer")
         if not (os.path.isdir(te_dir) and os.path.isdir(tok_dir)):
@@ -390,7 +391,11 @@ class QwenImagePipeline(nn.Module):
         dev = torch.device(device if device is not None else self.device)
         model = Qwen2_5_VLForConditionalGeneration.from_pretrained(te_dir, torch_dtype=BF16, local_files_only=True).to(dev).eval()
         tok = AutoTokenizer.from_pretrained(tok_dir, local_files_only=True)
-        self.text_encoder = QwenPromptEncoder(model, tok, dtype=BF16)
+        if getattr(self.od_config, "native_text_encoder", False):
+            # the decoder layers on this library's kernels; the HF copies are dropped as they are fused (13 GB are not held twice)
+            self.text_encoder = NativeQwenPromptEncoder.from_hf(model, tok, free_source=True)
+        else:
+            self.text_encoder = QwenPromptEncoder(model, tok, dtype=BF16)
 
     def encode_prompt(self, prompt, num_images_per_prompt: int = 1, prompt_embeds=None, prompt_embeds_mask=None,
                       max_sequence_length: int = 1024):

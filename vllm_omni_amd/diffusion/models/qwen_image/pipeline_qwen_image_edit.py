@@ -36,6 +36,9 @@ def calculate_dimensions(target_area: float, ratio: float) -> tuple[int, int, No
 class QwenImageEditPipeline(QwenImagePipeline):
     def __init__(self, *, od_config=None, prefix: str = "", device=None, transformer=None, vae=None, **kw):
         dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
+        if getattr(od_config, "native_text_encoder", False):
+            raise NotImplementedError(f"{type(self).__name__}: native_text_encoder=True covers text-only prompts; this pipeline's "
+                                      "prompts go through the HF model's vision tower / caption path - leave the flag off")
         super().__init__(od_config=od_config, prefix=prefix, device=dev, transformer=transformer,
                          vae=vae if vae is not None else AutoencoderKLQwenImage(device=dev, with_encoder=True), **kw)
         if not getattr(self.vae, "with_encoder", False):

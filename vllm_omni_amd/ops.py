@@ -462,6 +462,85 @@ def lora_merge(w_base, w_out, up, down, scale: float, *, row0: int = 0, rows: in
     return w_out
 
 
+def _need_text_encoder(what: str) -> None:
+    if not N.features() & N.FEATURE_TEXT_ENCODER:
+        raise N.OmniNativeError(f"this libomni_cdna4.so does not report OMNI_FEATURE_TEXT_ENCODER: it has no {what} (the native "
+                                "Qwen2.5-VL prompt encoder); there is no torch fallback")
+
+
+def text_rope_neox_(qkv, num_heads: int, num_kv_heads: int, cos_tab, sin_tab, row_pos, err=None):
+    """omni_text_rope_neox: rotate-half RoPE in place on the q and k column blocks of qkv [rows, >= (H + 2 H_kv) * 128] bf16 (a row
+    stride is honoured); cos_tab / sin_tab fp32 [npos, 64] contiguous, row_pos int32 [rows].  The v block is not touched.
+    `err` (int32 [1] on the device) is set when a position had to be clamped into the table."""
+    _need_text_encoder("omni_text_rope_neox")
+    rows, _, ld = _rows2d(qkv, "qkv")
+    if cos_tab.shape != sin_tab.shape or cos_tab.dim() != 2 or cos_tab.shape[1] != 64 or not (cos_tab.is_contiguous() and sin_tab.is_contiguous()):
+        raise N.OmniNativeError("text_rope_neox_: cos_tab / sin_tab are contiguous fp32 [npos, 64] tables")
+    if row_pos.numel() != rows:
+        raise N.OmniNativeError(f"text_rope_neox_: row_pos has {row_pos.numel()} entries for {rows} rows")
+    N.check(N.lib().omni_text_rope_neox(_p(qkv, name="qkv"), ld, rows, num_heads, num_kv_heads, _p(cos_tab, torch.float32, "cos"),
+                                        _p(sin_tab, torch.float32, "sin"), cos_tab.shape[0], _p(row_pos, torch.int32, "row_pos"),
+                                        _p(err, torch.int32, "err"), _stream()), "omni_text_rope_neox")
+    return qkv
+
+
+def text_swiglu(gate_up, out=None, *, out_k32_blocked: bool = False):
+    """omni_text_swiglu: gate_up [rows, 2 I] bf16 (gate | up, the fused GEMM's output) -> silu(gate) * up [rows, I];
+    out_k32_blocked: the result (same shape) holds the K32-blocked order [I/32][rows][32] for a GEMM's `a_k32_blocked`."""
+    _need_text_encoder("omni_text_swiglu")
+    rows, two_i, ld = _rows2d(gate_up, "gate_up")
+    if two_i % 2:
+        raise N.OmniNativeError("text_swiglu: gate_up has an odd number of columns")
+    y = torch.empty(rows, two_i // 2, dtype=BF16, device=gate_up.device) if out is None else out
+    if out_k32_blocked and not y.is_contiguous():
+        raise N.OmniNativeError("text_swiglu: a K32-blocked output is one contiguous buffer")
+    N.check(N.lib().omni_text_swiglu(_p(gate_up, name="gate_up"), ld, _p(y, name="out"), y.stride(0), rows, two_i // 2,
+                                     rows if out_k32_blocked else 0, _stream()), "omni_text_swiglu")
+    return y
+
+
+def text_embed_gather(table, ids, err, out=None):
+    """omni_text_embed_gather: out[r] = table[ids[r]] (table [vocab, D] bf16 contiguous, ids int32 [rows]); an id outside the
+    table writes a zero row and sets `err` (int32 [1] on the device) instead of reading."""
+    _need_text_encoder("omni_text_embed_gather")
+    vocab, D, ld = _rows2d(table, "table")
+    if ld != D:
+        raise N.OmniNativeError("text_embed_gather: the table must be contiguous")
+    y = torch.empty(ids.numel(), D, dtype=BF16, device=table.device) if out is None else out
+    N.check(N.lib().omni_text_embed_gather(_p(table, name="table"), vocab, D, _p(ids, torch.int32, "ids"), ids.numel(),
+                                           _p(y, name="out"), y.stride(0), _p(err, torch.int32, "err"), _stream()),
+            "omni_text_embed_gather")
+    return y
+
+
+def qwen2_text_workspace_bytes(weights: "N.TextWeights", total_rows: int) -> int:
+    _need_text_encoder("omni_qwen2_text_workspace_bytes")
+    return int(N.lib().omni_qwen2_text_workspace_bytes(C.byref(weights), int(total_rows)))
+
+
+def qwen2_text_forward(weights: "N.TextWeights", input_ids, cu_seqlens, row_pos, max_seqlen: int, workspace, out=None):
+    """omni_qwen2_text_forward: the whole Qwen2.5-VL text model over the packed tokens of `cu_seqlens.numel() - 1` prompts.
+    `weights`: the filled descriptor (models/qwen_image/text_encoder.py builds and owns it); input_ids / row_pos int32 [rows],
+    cu_seqlens int32 [n + 1], all on the device; `workspace`: uint8 device tensor of at least qwen2_text_workspace_bytes(...)
+    bytes whose first 256 bytes were zero when it was allocated.  -> last hidden state [rows, hidden] bf16."""
+    _need_text_encoder("omni_qwen2_text_forward")
+    rows = input_ids.numel()
+    if row_pos.numel() != rows:
+        raise N.OmniNativeError(f"qwen2_text_forward: row_pos has {row_pos.numel()} entries for {rows} tokens")
+    if not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise N.OmniNativeError("qwen2_text_forward: the workspace must be a contiguous uint8 DEVICE tensor")
+    y = torch.empty(rows, weights.hidden_size, dtype=BF16, device=input_ids.device) if out is None else out
+    if not y.is_contiguous():
+        raise N.OmniNativeError("qwen2_text_forward: out must be contiguous")
+    b = N.TextBatch()
+    b.n_prompts, b.total_rows, b.max_seqlen = cu_seqlens.numel() - 1, rows, int(max_seqlen)
+    b.input_ids, b.cu_seqlens = _p(input_ids, torch.int32, "input_ids"), _p(cu_seqlens, torch.int32, "cu_seqlens")
+    b.row_pos, b.out = _p(row_pos, torch.int32, "row_pos"), _p(y, name="out")
+    b.workspace, b.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    N.check(N.lib().omni_qwen2_text_forward(C.byref(weights), C.byref(b), _stream()), "omni_qwen2_text_forward")
+    return y
+
+
 def vae_conv2d(x, w, bias=None, *, gamma=None, silu=True, res=None, upsample2x=False, downsample2x=False, clamp=None,
                out=None, x_bordered=False, y_bordered=False, norm_gamma=None, norm_silu=True, keep_raw=True):
     """NHWC bf16 conv (3x3 pad 1 or 1x1): x [B,H,W,Cin], w [Cout,ks,ks,Cin].  downsample2x: the encoder's zero-pad
