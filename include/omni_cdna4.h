@@ -69,7 +69,12 @@ uint32_t omni_features(void);
  *
  * A_g  [M_g, K] bf16 row-major, row stride lda (elements); optional a_row_map[M_g] gathers rows.
  * W_g  [N, K]   bf16 row-major ([out, in], the nn.Linear layout; fused QKV rows ordered q|k|v).
- * K % 64 == 0 (else OMNI_ERR_UNSUPPORTED); M_g, N arbitrary (tails are predicated).
+ * K % 32 == 0 and N % 8 == 0 (else OMNI_ERR_UNSUPPORTED; K % 64 == 32 runs on the fallback kernel; fp8: K % 128 == 0); M_g >= 1
+ * arbitrary (row and column tails of a 256x256 tile are predicated).  Alignment (else OMNI_ERR_ALIGN): A, W 16 bytes and
+ * lda % 8 == 0; out 8 bytes and ldo % 4 == 0; GATE_RES ldres % 4 == 0 and gate_item_stride % 4 == 0.  The bias, res, gate,
+ * out1 and out2 POINTERS are not checked: the kernels read and write them as 8-byte vectors and assume 8-byte alignment.  Outputs,
+ * bias, residual and gate that are all 16-byte aligned with strides % 8 == 0 take the row-coalesced epilogue (required for
+ * K32-blocked outputs and SPLIT3_QKNORM_ROPE); anything less takes the fallback kernel's direct epilogue — the same bits.
  * ---------------------------------------------------------------------------------------------- */
 typedef enum {
   OMNI_EPI_BIAS = 0,          /* y = acc + bias                                              */

@@ -5,7 +5,8 @@
 //   3  gemm_bf16_pp_kernel   — the production kernel (default): BK = 64 K-tiles, the two wave groups of the workgroup run
 //      half a phase apart (one in an MFMA-only cluster while its SIMD partner issues reads and LDS-DMA), see its comment;
 //   1  gemm_bf16_ring_kernel — round 1's kernel, now the fallback for what the ping-pong kernel does not take (K % 64 != 0,
-//      operand offsets beyond 32 bits, outputs that cannot use the row-coalesced epilogue); bit-identical results.
+//      operand offsets beyond 32 bits, outputs that cannot use the row-coalesced epilogue); bit-identical results, with
+//      either of its epilogues (the direct one rounds acc + bias to bf16 before the gated residual, like the coalesced one).
 // Everything else that was built and measured against them — the first design (family 0), the hipcc-scheduled 4-wave kernel (2),
 // the hand-placed 4-wave kernels with the accumulators in the AGPR half (4 "Q4", 7 "V4": the vendor kernel's schedule), the
 // two-phase ping-pong variants (5, 6), the persistent ping-pong kernel (8), the ablation entry points and the phase probe — lives
@@ -165,7 +166,12 @@ OMNI_DEVINL omni_gemm_group pick_group(const omni_gemm_params& P, int gi) {
   return G;
 }
 
-template <int EPI, int NB, int MB>
+// Direct epilogue: every lane stores its own accumulator values (8 B per row and instruction).  BIAS_IN_ACC: the accumulators were
+// started at the bias (the ring kernel), so that the fp32 sum is formed in the same order as with the row-coalesced epilogue.
+// The dev-only kernels that end in it (-DOMNI_DEV: dev/gemm_family0_first_design.inc, the 4-wave kernel in
+// dev/gemm_family5_6_two_phase_pingpong_and_2_w4.inc) instantiate it with BIAS_IN_ACC = false; their GATE_RES result rounds
+// acc + bias to bf16 before the gated residual too, the documented rounding point.
+template <int EPI, int NB, int MB, bool BIAS_IN_ACC = false>
 OMNI_DEVINL void gemm_epilogue_t(const omni_gemm_params& P, const omni_gemm_group& G, f32x16_t (&acc)[NB][MB],
                                  int mrow0, int ncol0, int l31, int hi) {
   const int M = G.M, N = P.N;
@@ -186,7 +192,7 @@ OMNI_DEVINL void gemm_epilogue_t(const omni_gemm_params& P, const omni_gemm_grou
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = acc[nb][mb][q * 4 + j];
-        if (G.bias) {
+        if (!BIAS_IN_ACC && G.bias) {
           const u32x2_t b = *reinterpret_cast<const u32x2_t*>(G.bias + n);
           v[0] += bf16_lo(b[0]); v[1] += bf16_hi(b[0]); v[2] += bf16_lo(b[1]); v[3] += bf16_hi(b[1]);
         }
@@ -205,10 +211,12 @@ OMNI_DEVINL void gemm_epilogue_t(const omni_gemm_params& P, const omni_gemm_grou
         if (EPI == OMNI_EPI_BIAS_GATE_RES) {
           const u32x2_t g = *reinterpret_cast<const u32x2_t*>(G.gate + (int64_t)item * G.gate_item_stride + n);
           const u32x2_t r = *reinterpret_cast<const u32x2_t*>(G.res + orow * G.ldres + n);
-          v[0] = bf16_lo(r[0]) + bf16_lo(g[0]) * v[0];
-          v[1] = bf16_hi(r[0]) + bf16_hi(g[0]) * v[1];
-          v[2] = bf16_lo(r[1]) + bf16_lo(g[1]) * v[2];
-          v[3] = bf16_hi(r[1]) + bf16_hi(g[1]) * v[3];
+          // the documented rounding point (see the GATE_RES note below): c = bf16(acc + bias) first, then res + gate * c
+          const uint32_t c01 = pack_bf16x2(v[0], v[1]), c23 = pack_bf16x2(v[2], v[3]);
+          v[0] = bf16_lo(r[0]) + bf16_lo(g[0]) * bf16_lo(c01);
+          v[1] = bf16_hi(r[0]) + bf16_hi(g[0]) * bf16_hi(c01);
+          v[2] = bf16_lo(r[1]) + bf16_lo(g[1]) * bf16_lo(c23);
+          v[3] = bf16_hi(r[1]) + bf16_hi(g[1]) * bf16_hi(c23);
         }
         u32x2_t o;
         o[0] = pack_bf16x2(v[0], v[1]);
@@ -219,10 +227,10 @@ OMNI_DEVINL void gemm_epilogue_t(const omni_gemm_params& P, const omni_gemm_grou
   }
 }
 
-template <int EPI>
+template <int EPI, bool BIAS_IN_ACC = false>
 OMNI_DEVINL void gemm_epilogue(const omni_gemm_params& P, const omni_gemm_group& G, f32x16_t (&acc)[2][4], int m0,
                                int n0, int wm, int wn, int l31, int hi) {
-  gemm_epilogue_t<EPI, 2, 4>(P, G, acc, m0 + wm * 128, n0 + wn * 64, l31, hi);
+  gemm_epilogue_t<EPI, 2, 4, BIAS_IN_ACC>(P, G, acc, m0 + wm * 128, n0 + wn * 64, l31, hi);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -744,8 +752,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_ring_kernel(const omni_
     w_base[ks] = (wn * 64 + l31) * 64 + chunk;
   }
 
-  // The accumulators start at the BIAS (coalesced epilogue) instead of 0: same cost as the zero fill, and the epilogue's 128
-  // adds + 128 bf16 unpacks per lane (with all 8 waves in the epilogue at once) disappear.
+  // The accumulators start at the BIAS instead of 0: same cost as the zero fill, and the epilogue's 128 adds + 128 bf16 unpacks
+  // per lane (with all 8 waves in the epilogue at once) disappear.  Both epilogues rely on it, so that the direct one forms the
+  // same fp32 sum in the same order as the coalesced one (tests/test_gpu_gemm_elementwise.py compares their bits).
   f32x16_t acc[2][4];
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb) {
@@ -754,7 +763,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_ring_kernel(const omni_
     for (int q = 0; q < 4; ++q) {
       const int n = n0 + wn * 64 + hi * 4 + nb * 32 + q * 8;
       u32x2_t b = {0u, 0u};
-      if (COALESCED && G.bias && n < N) b = *reinterpret_cast<const u32x2_t*>(G.bias + n);
+      if (G.bias && n < N) b = *reinterpret_cast<const u32x2_t*>(G.bias + n);
       bini[q * 4 + 0] = bf16_lo(b[0]); bini[q * 4 + 1] = bf16_hi(b[0]);
       bini[q * 4 + 2] = bf16_lo(b[1]); bini[q * 4 + 3] = bf16_hi(b[1]);
     }
@@ -874,7 +883,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_ring_kernel(const omni_
 #undef OMNI_RING_PAIR
 
   if (COALESCED) gemm_epilogue_lds<EPI>(P, G, acc, m0, n0, wm, wn, l31, hi, smem, tid);
-  else gemm_epilogue<EPI>(P, G, acc, m0, n0, wm, wn, l31, hi);
+  else gemm_epilogue<EPI, true>(P, G, acc, m0, n0, wm, wn, l31, hi);
   if (bid + (int)gridDim.x < nwg) __syncthreads();   // the next tile's DMA reuses the LDS the epilogue has just read
   }  // tile loop
 }
