@@ -56,6 +56,8 @@ const char* omni_status_string(int status);
 #define OMNI_FEATURE_CFG_EULER_RAGGED 4u /* the library exports omni_cfg_euler_step_ragged: a function pointer, see there */
 #define OMNI_FEATURE_LORA_MERGE 8u /* the library exports omni_lora_merge: a function pointer, see there */
 #define OMNI_FEATURE_TEXT_ENCODER 16u /* the library exports omni_qwen2_text_forward and its companions: function pointers */
+#define OMNI_FEATURE_VISION_ENCODER 32u /* the library exports omni_qwen2_vision_forward, omni_qwen2_text_forward_mm and their
+                                        * companions: function pointers */
 uint32_t omni_features(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -566,6 +568,120 @@ extern int (*const omni_text_swiglu)(const omni_bf16* gate_up, int64_t ldgu, omn
 /* omni_text_embed_gather: h[r, :] = table[ids[r], :]; an id outside [0, vocab) writes zeros and sets *err (DEVICE int32) to 1. */
 extern int (*const omni_text_embed_gather)(const omni_bf16* table, int32_t vocab, int32_t D, const int32_t* ids, int32_t rows,
                                            omni_bf16* h, int64_t ldh, int32_t* err, omni_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Prompts WITH pictures (the Edit pipelines, pipeline_qwen_image_edit.py:352-397 / pipeline_qwen_image_edit_plus.py:274-330): the
+ * Qwen2.5-VL vision tower (HF `Qwen2_5_VisionTransformerPretrainedModel`: 32 blocks at hidden 1280 / 16 heads of 80 /
+ * intermediate 3420, patch merger to 3584) as one native call, and the text forward with real M-RoPE and the image embeddings
+ * in the token rows (optional symbols of ABI v14: ask omni_features() & OMNI_FEATURE_VISION_ENCODER; const function POINTERS
+ * like omni_qwen2_text_forward, for the same reason).
+ *
+ * The tower runs over the packed patch rows of all pictures IN WINDOW ORDER (the host permutes the processor's pixel_values
+ * rows by HF's window_index: the patch embedding is row-wise, so that equals HF's reorder behind it).  Per block: RMSNorm ->
+ * fused qkv GEMM (+ bias) -> omni_vision_rope_pad -> omni_flash_attn_general (head_dim 128, softmax_scale head_dim^-0.5,
+ * non-causal, cu_window or - full_attention - cu_image) -> projection + bias + residual -> RMSNorm -> fused gate|up GEMM
+ * (+ bias) -> omni_text_swiglu -> down + bias + residual.  Merger: RMSNorm per patch row -> [rows / 4, 4 D] -> GEMM + bias ->
+ * omni_gelu_erf -> GEMM + bias -> [rows / 4, out_hidden_size], still in window order.
+ * Zero padding done ONCE by the host, exact: the patch vector (3 * 2 * 14 * 14 = 1176) to patch_k in pixels and patch_w; the
+ * projection's K from head_dim to 128 columns per head; the intermediate size to a multiple of 64 in gate_up_w / gate_up_b
+ * (rows) and down_w (columns).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct omni_vision_layer_weights {
+  const omni_bf16* norm1_w;     /* [D] */
+  const omni_bf16* qkv_w;       /* [3 * H * head_dim, D]: HF attn.qkv as it is (q | k | v, each H heads of head_dim) */
+  const omni_bf16* qkv_b;       /* [3 * H * head_dim] */
+  const omni_bf16* proj_w;      /* [D, H * 128]: column h * 128 + j is HF's column h * head_dim + j, zero for j >= head_dim */
+  const omni_bf16* proj_b;      /* [D] */
+  const omni_bf16* norm2_w;     /* [D] */
+  const omni_bf16* gate_up_w;   /* [2 I, D]: rows of gate_proj | up_proj, each zero-padded to I rows */
+  const omni_bf16* gate_up_b;   /* [2 I] */
+  const omni_bf16* down_w;      /* [D, I]: zero-padded columns */
+  const omni_bf16* down_b;      /* [D] */
+  int32_t full_attention;       /* 1: this block attends over whole pictures (cu_image), 0: inside windows (cu_window) */
+  int32_t reserved;             /* 0 */
+} omni_vision_layer_weights;
+
+typedef struct omni_vision_weights {
+  int32_t num_layers, hidden_size, num_heads, head_dim; /* head_dim: a multiple of 16, <= 128, num_heads * head_dim = hidden */
+  int32_t intermediate_size;    /* I: the PADDED intermediate size, a multiple of 64 */
+  int32_t patch_k;              /* the padded patch vector, a multiple of 64 */
+  int32_t out_hidden_size;      /* a multiple of 64 */
+  int32_t gemm_w_k32_blocked;   /* 1: every GEMM weight (patch_w, qkv_w, proj_w, gate_up_w, down_w, merger_fc1_w, merger_fc2_w) is K32-blocked */
+  float rms_norm_eps;
+  int32_t reserved;             /* 0 */
+  const omni_bf16* patch_w;     /* [D, patch_k]: the Conv3d kernel flattened (no bias) */
+  const omni_bf16* ones;        /* [D] bf16 1.0 (the gate of the residual adds) */
+  const omni_bf16* merger_norm_w; /* [D] */
+  const omni_bf16* merger_fc1_w;  /* [4 D, 4 D] */
+  const omni_bf16* merger_fc1_b;  /* [4 D] */
+  const omni_bf16* merger_fc2_w;  /* [out_hidden_size, 4 D] */
+  const omni_bf16* merger_fc2_b;  /* [out_hidden_size] */
+  const omni_vision_layer_weights* layers; /* HOST array [num_layers] */
+} omni_vision_weights;
+
+typedef struct omni_vision_batch {
+  int32_t rows;                 /* patch rows of all pictures, a multiple of 4 (the 2 x 2 merge units are 4 consecutive rows) */
+  int32_t n_windows, n_images;
+  int32_t max_window, max_image; /* at least the longest window / picture in rows (they size the attention grids) */
+  int32_t reserved;             /* 0 */
+  const omni_bf16* pixels;      /* [rows, patch_k] the processor's pixel_values in window order, zero-padded columns */
+  const int32_t* cu_window;     /* DEVICE [n_windows + 1] prefix sums of the window lengths (no empty window) */
+  const int32_t* cu_image;      /* DEVICE [n_images + 1] prefix sums of the pictures' rows */
+  const float* rope_cos;        /* DEVICE [rows, head_dim / 2] fp32, per row: see omni_vision_rope_pad */
+  const float* rope_sin;
+  omni_bf16* out;               /* [rows / 4, out_hidden_size] */
+  void* workspace;              /* DEVICE, 16-byte aligned, as many bytes as omni_qwen2_vision_workspace_bytes answers for (w, rows) */
+  size_t workspace_bytes;
+} omni_vision_batch;
+/* One call enqueues the whole tower on `stream`; no allocation, no host read.  Status before any launch: null pointer,
+ * non-positive count, max_window / max_image above rows, num_heads * head_dim != hidden_size, short workspace ->
+ * OMNI_ERR_BAD_ARG; head_dim not a multiple of 16 or above 128, hidden_size / intermediate_size / patch_k / out_hidden_size
+ * not a multiple of 64, hidden_size > 8192, rows not a multiple of 4 -> OMNI_ERR_UNSUPPORTED; a workspace or output that is
+ * not 16-byte aligned -> OMNI_ERR_ALIGN. */
+extern int (*const omni_qwen2_vision_forward)(const omni_vision_weights* w, const omni_vision_batch* b, omni_stream stream);
+/* 0 for weights the forward refuses */
+extern size_t (*const omni_qwen2_vision_workspace_bytes)(const omni_vision_weights* w, int32_t rows);
+/* omni_vision_rope_pad: qkv [rows, ld_in >= 3 * H * hd] (the fused GEMM's output: q | k | v, each H heads of hd) ->
+ * out [rows, ld_out >= 3 * H * 128]: q | k | v, each H heads of 128 columns.  hd: a multiple of 16, <= 128.  For a q or k head x
+ * and the row's tables c = cos[row], s = sin[row] (fp32 [rows, hd / 2], built by the host: HF `apply_rotary_pos_emb_vision`):
+ *   y[i] = x[i] c[i] - x[i + hd/2] s[i],  y[i + hd/2] = x[i + hd/2] c[i] + x[i] s[i]   (i < hd / 2; fp32, one rounding to bf16)
+ * v is copied bit for bit; columns hd .. 127 of every head are written as zeros, so that attention at head size 128 with
+ * softmax_scale hd^-0.5 IS attention at head size hd. */
+extern int (*const omni_vision_rope_pad)(const omni_bf16* qkv, int64_t ld_in, omni_bf16* out, int64_t ld_out, int32_t rows,
+                                         int32_t H, int32_t hd, const float* cos_tab, const float* sin_tab, omni_stream stream);
+/* omni_gelu_erf: y = 0.5 x (1 + erf(x / sqrt 2)) (torch.nn.GELU(), NOT the tanh form of OMNI_EPI_BIAS_GELU_TANH) on [rows, n],
+ * n % 8 == 0; y row-major (ldy; y == x with ldy == ldx is in place) or, y_k32_rows = R >= rows, K32-blocked [n / 32][R][32]
+ * (n % 32 == 0, y != x). */
+extern int (*const omni_gelu_erf)(const omni_bf16* x, int64_t ldx, omni_bf16* y, int64_t ldy, int32_t rows, int32_t n,
+                                  int32_t y_k32_rows, omni_stream stream);
+/* omni_text_mrope: omni_text_rope_neox with Qwen2.5-VL's three position rows: rotary pair i of a head reads the tables at
+ * row_pos3[sec(i)][row], sec(i) = 0 (temporal) for i < s0, 1 (height) for i < s0 + s1, else 2 (width), with
+ * mrope_section = {s0, s1, s2}, s0 + s1 + s2 = 64, each a multiple of 8 (else OMNI_ERR_UNSUPPORTED; the checkpoints have
+ * 16, 24, 24).  row_pos3: DEVICE [3][rows].  With three equal rows the output equals omni_text_rope_neox's bit for bit. */
+extern int (*const omni_text_mrope)(omni_bf16* qkv, int64_t ld, int32_t rows, int32_t H, int32_t H_kv, const float* cos_tab,
+                                    const float* sin_tab, int32_t npos, const int32_t* row_pos3, const int32_t* mrope_section,
+                                    int32_t* err, omni_stream stream);
+
+typedef struct omni_text_batch_mm {
+  int32_t n_prompts, total_rows, max_seqlen, reserved; /* as in omni_text_batch */
+  const int32_t* input_ids;
+  const int32_t* cu_seqlens;
+  const int32_t* row_pos;        /* not read (row_pos3 takes its place); may be null */
+  omni_bf16* out;
+  void* workspace;               /* as in omni_text_batch, sized by omni_qwen2_text_workspace_bytes */
+  size_t workspace_bytes;
+  const int32_t* row_pos3;       /* DEVICE [3][total_rows]: temporal, height, width position of every token (HF get_rope_index) */
+  const omni_bf16* vision_rows;  /* DEVICE [n_vision_rows, D]: the vision tower's output; null with n_vision_rows = 0 */
+  const int32_t* vision_row_of;  /* DEVICE [total_rows]: >= 0: the token row takes vision_rows[that row] instead of its token
+                                  * embedding (HF's masked_scatter, with any permutation of the rows folded in); -1: the token
+                                  * embedding; null with n_vision_rows = 0 */
+  int32_t n_vision_rows;
+  int32_t mrope_section[3];      /* see omni_text_mrope */
+} omni_text_batch_mm;
+/* omni_qwen2_text_forward with the two additions; the same driver, statuses and error word.  A vision_row_of entry outside
+ * [-1, n_vision_rows) yields a ZERO row (never a read) and sets the error word.  With n_vision_rows = 0 and three equal position
+ * rows the launches and the output are those of omni_qwen2_text_forward, bit for bit. */
+extern int (*const omni_qwen2_text_forward_mm)(const omni_text_weights* w, const omni_text_batch_mm* b, omni_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * VAE kernels (AutoencoderKLQwenImage.decode — and .encode for the Edit pipelines — for one frame,

@@ -125,6 +125,42 @@ class TextBatch(C.Structure):
     ]
 
 
+class TextBatchMm(C.Structure):
+    """omni_text_batch_mm: omni_text_batch plus the three M-RoPE position rows and the vision rows of the picture tokens."""
+    _fields_ = TextBatch._fields_ + [
+        ("row_pos3", c_i32_p), ("vision_rows", c_bf16_p), ("vision_row_of", c_i32_p),
+        ("n_vision_rows", C.c_int32), ("mrope_section", C.c_int32 * 3),
+    ]
+
+
+class VisionLayerWeights(C.Structure):
+    """omni_vision_layer_weights: device pointers of one Qwen2.5-VL vision block (padded as the header says)."""
+    _fields_ = [(n, c_bf16_p) for n in ("norm1_w", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "gate_up_w", "gate_up_b",
+                                        "down_w", "down_b")] + [("full_attention", C.c_int32), ("reserved", C.c_int32)]
+
+
+class VisionWeights(C.Structure):
+    """omni_vision_weights: geometry, patch embedding, merger and the HOST array of blocks of omni_qwen2_vision_forward."""
+    _fields_ = [
+        ("num_layers", C.c_int32), ("hidden_size", C.c_int32), ("num_heads", C.c_int32), ("head_dim", C.c_int32),
+        ("intermediate_size", C.c_int32), ("patch_k", C.c_int32), ("out_hidden_size", C.c_int32), ("gemm_w_k32_blocked", C.c_int32),
+        ("rms_norm_eps", C.c_float), ("reserved", C.c_int32),
+        ("patch_w", c_bf16_p), ("ones", c_bf16_p), ("merger_norm_w", c_bf16_p), ("merger_fc1_w", c_bf16_p),
+        ("merger_fc1_b", c_bf16_p), ("merger_fc2_w", c_bf16_p), ("merger_fc2_b", c_bf16_p),
+        ("layers", C.POINTER(VisionLayerWeights)),
+    ]
+
+
+class VisionBatch(C.Structure):
+    """omni_vision_batch: the packed patch rows of all pictures in window order, their windows, pictures and RoPE tables."""
+    _fields_ = [
+        ("rows", C.c_int32), ("n_windows", C.c_int32), ("n_images", C.c_int32), ("max_window", C.c_int32),
+        ("max_image", C.c_int32), ("reserved", C.c_int32),
+        ("pixels", c_bf16_p), ("cu_window", c_i32_p), ("cu_image", c_i32_p), ("rope_cos", c_f32_p), ("rope_sin", c_f32_p),
+        ("out", c_bf16_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 class ConvParams(C.Structure):
     _fields_ = [
         ("x", c_bf16_p), ("w", c_bf16_p), ("bias", c_bf16_p), ("gamma", c_bf16_p), ("res", c_bf16_p), ("y", c_bf16_p),
@@ -279,6 +315,14 @@ FEATURE_PROTOTYPES = {
     "omni_text_swiglu": (C.c_int, [c_bf16_p, C.c_int64, c_bf16_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p], 16),
     "omni_text_embed_gather": (C.c_int, [c_bf16_p, C.c_int32, C.c_int32, c_i32_p, C.c_int32, c_bf16_p, C.c_int64, c_i32_p,
                                          C.c_void_p], 16),
+    "omni_qwen2_vision_forward": (C.c_int, [C.POINTER(VisionWeights), C.POINTER(VisionBatch), C.c_void_p], 32),
+    "omni_qwen2_vision_workspace_bytes": (C.c_size_t, [C.POINTER(VisionWeights), C.c_int32], 32),
+    "omni_vision_rope_pad": (C.c_int, [c_bf16_p, C.c_int64, c_bf16_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_f32_p, c_f32_p,
+                                       C.c_void_p], 32),
+    "omni_gelu_erf": (C.c_int, [c_bf16_p, C.c_int64, c_bf16_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p], 32),
+    "omni_text_mrope": (C.c_int, [c_bf16_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_f32_p, c_f32_p, C.c_int32, c_i32_p,
+                                  C.POINTER(C.c_int32), c_i32_p, C.c_void_p], 32),
+    "omni_qwen2_text_forward_mm": (C.c_int, [C.POINTER(TextWeights), C.POINTER(TextBatchMm), C.c_void_p], 32),
 }
 
 # symbols a library of the SAME ABI version may lack: they were added together with a field that went into former struct
@@ -289,6 +333,7 @@ FEATURE_TEACACHE_RAGGED = 2                       # OMNI_FEATURE_TEACACHE_RAGGED
 FEATURE_CFG_EULER_RAGGED = 4                      # OMNI_FEATURE_CFG_EULER_RAGGED: omni_cfg_euler_step_ragged is exported
 FEATURE_LORA_MERGE = 8                            # OMNI_FEATURE_LORA_MERGE: omni_lora_merge is exported
 FEATURE_TEXT_ENCODER = 16                         # OMNI_FEATURE_TEXT_ENCODER: omni_qwen2_text_forward and its companions are exported
+FEATURE_VISION_ENCODER = 32                       # OMNI_FEATURE_VISION_ENCODER: omni_qwen2_vision_forward, omni_qwen2_text_forward_mm and companions
 ELEM_BF16, ELEM_F16 = 0, 1                        # omni_attn_params.elem_type
 
 _lib = None

@@ -8,12 +8,15 @@
 //   text_rope_neox_kernel    rotate-half (NeoX) RoPE in place on the q and k column blocks of the fused QKV buffer.  A text-only
 //                            prompt gives the three M-RoPE position rows (temporal, height, width) EQUAL values, so whatever
 //                            mrope_section selects, every rotary pair of a token sees the same position: this kernel IS
-//                            Qwen2.5-VL's multimodal rotary embedding for such prompts.  (Prompts with pictures - the Edit
-//                            pipelines - have unequal rows and do not come here.)
+//                            Qwen2.5-VL's multimodal rotary embedding for such prompts.
+//   text_mrope_kernel        the same with three position rows and mrope_section: prompts with pictures (the Edit pipelines,
+//                            omni_qwen2_text_forward_mm); with equal rows it reproduces text_rope_neox_kernel bit for bit.
 //                            bytes/row = 2 x 2 x (H + H_kv) x 128 + the row's 512 B of the cos / sin tables (L2-resident).
 //   text_swiglu_kernel       y = silu(gate) * up from the [rows, 2 I] output of the fused gate|up GEMM, row-major or K32-blocked.
 //                            bytes/row = 2 x 2 I read + 2 I written.
 //   text_embed_gather_kernel h[r] = E[ids[r]]; an id outside [0, vocab) writes zeros and raises the error word, it never reads.
+//   text_embed_gather_mm_kernel  ... or h[r] = V[vision_row_of[r]] where that is >= 0: the vision tower's rows scattered into the
+//                            picture tokens, with the same rule for an index outside the rows.
 #include "common.h"
 
 namespace {
@@ -36,29 +39,11 @@ OMNI_DEVINL u32x4_t pack8(const float* f) {
   return w;
 }
 
-// 8 lanes per head: lane j of a head holds elements 8 j .. 8 j + 7 AND their partners 64 + 8 j .. of the rotate-half pairs, so a
-// wave covers 8 heads of one row and nothing crosses lanes.  unit = row * nseg + segment of 8 heads.
-__global__ __launch_bounds__(256) void text_rope_neox_kernel(uint16_t* __restrict__ qkv, int64_t ld, int rows, int H, int H_kv,
-                                                             const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
-                                                             int npos, const int32_t* __restrict__ row_pos, int32_t* __restrict__ err) {
+// the rotation of one lane's 8 pairs (i, i + 64) of one head: x points at element 8 j of the head, cp / sp at column 8 j of the
+// position's table rows.  Shared by the one-position and the three-position kernel: the same loads and the same arithmetic.
+OMNI_DEVINL void rope_rotate8(uint16_t* x, const float* cp, const float* sp) {
 #pragma clang fp contract(off)
-  const int lane = threadIdx.x & 63;
-  const int nheads = H + H_kv, nseg = (nheads + 7) >> 3;
-  const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t row = unit / nseg;
-  if (row >= rows) return;
-  const int head = (int)(unit - row * nseg) * 8 + (lane >> 3);
-  if (head >= nheads) return;
-  const int j = lane & 7;
-  int p = row_pos[row];
-  if (p < 0 || p >= npos) {                // never an out-of-range read of the tables: clamp, and say so
-    if (err && j == 0) *err = 2;
-    p = p < 0 ? 0 : npos - 1;
-  }
-  uint16_t* x = qkv + row * ld + (int64_t)head * TEXT_HEAD + 8 * j;
   const u32x4_t lo = *reinterpret_cast<const u32x4_t*>(x), hi = *reinterpret_cast<const u32x4_t*>(x + 64);
-  const float* cp = cos_tab + (int64_t)p * 64 + 8 * j;
-  const float* sp = sin_tab + (int64_t)p * 64 + 8 * j;
   const f32x4_t c0 = *reinterpret_cast<const f32x4_t*>(cp), c1 = *reinterpret_cast<const f32x4_t*>(cp + 4);
   const f32x4_t s0 = *reinterpret_cast<const f32x4_t*>(sp), s1 = *reinterpret_cast<const f32x4_t*>(sp + 4);
   float a[8], b[8], oa[8], ob[8];
@@ -72,6 +57,51 @@ __global__ __launch_bounds__(256) void text_rope_neox_kernel(uint16_t* __restric
   }
   *reinterpret_cast<u32x4_t*>(x) = pack8(oa);
   *reinterpret_cast<u32x4_t*>(x + 64) = pack8(ob);
+}
+
+// 8 lanes per head: lane j of a head holds elements 8 j .. 8 j + 7 AND their partners 64 + 8 j .. of the rotate-half pairs, so a
+// wave covers 8 heads of one row and nothing crosses lanes.  unit = row * nseg + segment of 8 heads.
+__global__ __launch_bounds__(256) void text_rope_neox_kernel(uint16_t* __restrict__ qkv, int64_t ld, int rows, int H, int H_kv,
+                                                             const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
+                                                             int npos, const int32_t* __restrict__ row_pos, int32_t* __restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int nheads = H + H_kv, nseg = (nheads + 7) >> 3;
+  const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t row = unit / nseg;
+  if (row >= rows) return;
+  const int head = (int)(unit - row * nseg) * 8 + (lane >> 3);
+  if (head >= nheads) return;
+  const int j = lane & 7;
+  int p = row_pos[row];
+  if (p < 0 || p >= npos) {                // never an out-of-range read of the tables: clamp, and say so
+    if (err && j == 0) *err = 2;
+    p = p < 0 ? 0 : npos - 1;
+  }
+  rope_rotate8(qkv + row * ld + (int64_t)head * TEXT_HEAD + 8 * j, cos_tab + (int64_t)p * 64 + 8 * j, sin_tab + (int64_t)p * 64 + 8 * j);
+}
+
+// Qwen2.5-VL's multimodal RoPE: the same kernel with three position rows [3][rows]; pairs 0 .. s0 - 1 of a head read the tables
+// at the temporal position, s0 .. s0 + s1 - 1 at the height, the rest at the width position.  The sections are multiples of 8, so
+// the 8 pairs of a lane lie in ONE section and the lane still reads one table row.
+__global__ __launch_bounds__(256) void text_mrope_kernel(uint16_t* __restrict__ qkv, int64_t ld, int rows, int H, int H_kv,
+                                                         const float* __restrict__ cos_tab, const float* __restrict__ sin_tab, int npos,
+                                                         const int32_t* __restrict__ row_pos3, int s0, int s01,
+                                                         int32_t* __restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int nheads = H + H_kv, nseg = (nheads + 7) >> 3;
+  const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t row = unit / nseg;
+  if (row >= rows) return;
+  const int head = (int)(unit - row * nseg) * 8 + (lane >> 3);
+  if (head >= nheads) return;
+  const int j = lane & 7;
+  const int sec = 8 * j < s0 ? 0 : (8 * j < s01 ? 1 : 2);
+  int p = row_pos3[(int64_t)sec * rows + row];
+  if (p < 0 || p >= npos) {
+    if (err) *err = 2;
+    p = p < 0 ? 0 : npos - 1;
+  }
+  rope_rotate8(qkv + row * ld + (int64_t)head * TEXT_HEAD + 8 * j, cos_tab + (int64_t)p * 64 + 8 * j, sin_tab + (int64_t)p * 64 + 8 * j);
 }
 
 // unit = row * nseg + segment of 512 columns; a lane owns 8 consecutive columns of gate and the same 8 of up
@@ -115,6 +145,40 @@ __global__ __launch_bounds__(256) void text_embed_gather_kernel(const uint16_t* 
   *reinterpret_cast<u32x4_t*>(h + row * ldh + e) = v;
 }
 
+// the same with the picture rows: a token row whose vision_row_of entry is >= 0 takes that row of the vision tower's output in
+// place of its token embedding (HF's masked_scatter); an entry outside [-1, n_vision) writes zeros and raises the error word
+__global__ __launch_bounds__(256) void text_embed_gather_mm_kernel(const uint16_t* __restrict__ table, int vocab, int D,
+                                                                   const int32_t* __restrict__ ids,
+                                                                   const uint16_t* __restrict__ vision, int n_vision,
+                                                                   const int32_t* __restrict__ vision_row_of, int rows,
+                                                                   uint16_t* __restrict__ h, int64_t ldh, int32_t* __restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int nseg = (D + 511) >> 9;
+  const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t row = unit / nseg;
+  if (row >= rows) return;
+  const int seg = (int)(unit - row * nseg);
+  const int e = (seg * 64 + lane) * 8;
+  const int vr = vision_row_of[row];
+  const uint16_t* src = nullptr;
+  int code = 0;
+  if (vr >= 0) {
+    if (vr < n_vision) src = vision + (int64_t)vr * D;
+    else code = 3;
+  } else if (vr == -1) {
+    const int id = ids[row];
+    if (id >= 0 && id < vocab) src = table + (int64_t)id * D;
+    else code = 1;
+  } else {
+    code = 3;
+  }
+  if (code && err && seg == 0 && lane == 0) *err = code;
+  if (e >= D) return;
+  u32x4_t v = {0u, 0u, 0u, 0u};
+  if (src) v = *reinterpret_cast<const u32x4_t*>(src + e);
+  *reinterpret_cast<u32x4_t*>(h + row * ldh + e) = v;
+}
+
 inline unsigned wave_blocks(int64_t units) { return (unsigned)((units + 3) / 4); }
 
 int text_rope_neox(omni_bf16* qkv, int64_t ld, int32_t rows, int32_t H, int32_t H_kv, const float* cos_tab, const float* sin_tab,
@@ -126,6 +190,21 @@ int text_rope_neox(omni_bf16* qkv, int64_t ld, int32_t rows, int32_t H, int32_t 
   if (units > 0x7fffffffLL) return OMNI_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(text_rope_neox_kernel, dim3(wave_blocks(units)), dim3(256), 0, static_cast<hipStream_t>(stream), qkv, ld, rows,
                      H, H_kv, cos_tab, sin_tab, npos, row_pos, err);
+  OMNI_CHECK_LAUNCH();
+  return OMNI_OK;
+}
+
+int text_mrope(omni_bf16* qkv, int64_t ld, int32_t rows, int32_t H, int32_t H_kv, const float* cos_tab, const float* sin_tab,
+               int32_t npos, const int32_t* row_pos3, const int32_t* sec, int32_t* err, omni_stream stream) {
+  if (!qkv || !cos_tab || !sin_tab || !row_pos3 || !sec || rows <= 0 || H <= 0 || H_kv <= 0 || npos <= 0) return OMNI_ERR_BAD_ARG;
+  if (ld < (int64_t)(H + 2 * H_kv) * TEXT_HEAD) return OMNI_ERR_BAD_ARG;
+  if (sec[0] < 0 || sec[1] < 0 || sec[2] < 0 || (int64_t)sec[0] + sec[1] + sec[2] != TEXT_HEAD / 2) return OMNI_ERR_BAD_ARG;
+  if (sec[0] % 8 || sec[1] % 8 || sec[2] % 8) return OMNI_ERR_UNSUPPORTED;
+  if (!omni_aligned16(qkv) || !omni_aligned16(cos_tab) || !omni_aligned16(sin_tab) || (ld % 8)) return OMNI_ERR_ALIGN;
+  const int64_t units = (int64_t)rows * ((H + H_kv + 7) / 8);
+  if (units > 0x7fffffffLL) return OMNI_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(text_mrope_kernel, dim3(wave_blocks(units)), dim3(256), 0, static_cast<hipStream_t>(stream), qkv, ld, rows, H,
+                     H_kv, cos_tab, sin_tab, npos, row_pos3, sec[0], sec[0] + sec[1], err);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }
@@ -153,6 +232,21 @@ int text_embed_gather(const omni_bf16* table, int32_t vocab, int32_t D, const in
   if (units > 0x7fffffffLL) return OMNI_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(text_embed_gather_kernel, dim3(wave_blocks(units)), dim3(256), 0, static_cast<hipStream_t>(stream), table, vocab,
                      D, ids, rows, h, ldh, err);
+  OMNI_CHECK_LAUNCH();
+  return OMNI_OK;
+}
+
+int text_embed_gather_mm(const omni_bf16* table, int32_t vocab, int32_t D, const int32_t* ids, const omni_bf16* vision,
+                         int32_t n_vision, const int32_t* vision_row_of, int32_t rows, omni_bf16* h, int64_t ldh, int32_t* err,
+                         omni_stream stream) {
+  if (!table || !ids || !h || !err || !vision || !vision_row_of || vocab <= 0 || D <= 0 || rows <= 0 || n_vision <= 0 || ldh < D)
+    return OMNI_ERR_BAD_ARG;
+  if (D % 8) return OMNI_ERR_UNSUPPORTED;
+  if (!omni_aligned16(table) || !omni_aligned16(vision) || !omni_aligned16(h) || (ldh % 8)) return OMNI_ERR_ALIGN;
+  const int64_t units = (int64_t)rows * ((D + 511) / 512);
+  if (units > 0x7fffffffLL) return OMNI_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(text_embed_gather_mm_kernel, dim3(wave_blocks(units)), dim3(256), 0, static_cast<hipStream_t>(stream), table,
+                     vocab, D, ids, vision, n_vision, vision_row_of, rows, h, ldh, err);
   OMNI_CHECK_LAUNCH();
   return OMNI_OK;
 }
@@ -227,10 +321,29 @@ int residual_gemm(const omni_text_weights* w, const TextWorkspace& ws, const omn
   return omni_gemm_bf16(&p, stream);
 }
 
-int text_forward(const omni_text_weights* w, const omni_text_batch* b, omni_stream stream) {
-  if (!b) return OMNI_ERR_BAD_ARG;
+// what omni_qwen2_text_forward_mm adds to a batch; null for omni_qwen2_text_forward
+struct TextMm {
+  const int32_t* row_pos3;
+  const int32_t* section;
+  const omni_bf16* vision_rows;
+  const int32_t* vision_row_of;
+  int32_t n_vision_rows;
+};
+
+// the one driver of both entry points: `b` holds the fields the two batch structs share
+int text_forward_impl(const omni_text_weights* w, const omni_text_batch* b, const TextMm* mm, omni_stream stream) {
   OMNI_TRY_STATUS(text_check_weights(w));
-  if (!b->input_ids || !b->cu_seqlens || !b->row_pos || !b->out || !b->workspace) return OMNI_ERR_BAD_ARG;
+  if (!b->input_ids || !b->cu_seqlens || !b->out || !b->workspace) return OMNI_ERR_BAD_ARG;
+  if (mm) {
+    if (!mm->row_pos3 || mm->n_vision_rows < 0 || (mm->n_vision_rows > 0 && (!mm->vision_rows || !mm->vision_row_of)))
+      return OMNI_ERR_BAD_ARG;
+    const int32_t* sec = mm->section;
+    if (sec[0] < 0 || sec[1] < 0 || sec[2] < 0 || (int64_t)sec[0] + sec[1] + sec[2] != TEXT_HEAD / 2) return OMNI_ERR_BAD_ARG;
+    if (sec[0] % 8 || sec[1] % 8 || sec[2] % 8) return OMNI_ERR_UNSUPPORTED;
+    if (mm->vision_rows && !omni_aligned16(mm->vision_rows)) return OMNI_ERR_ALIGN;
+  } else if (!b->row_pos) {
+    return OMNI_ERR_BAD_ARG;
+  }
   if (b->n_prompts <= 0 || b->total_rows <= 0 || b->max_seqlen <= 0 || b->max_seqlen > b->total_rows) return OMNI_ERR_BAD_ARG;
   if (b->n_prompts > TEXT_MAX_PROMPTS) return OMNI_ERR_UNSUPPORTED;
   if (!omni_aligned16(b->workspace) || !omni_aligned16(b->out)) return OMNI_ERR_ALIGN;
@@ -254,7 +367,11 @@ int text_forward(const omni_text_weights* w, const omni_text_batch* b, omni_stre
     return OMNI_ERR_BAD_ARG;
   }
 
-  OMNI_TRY_STATUS(text_embed_gather(w->embed_tokens, w->vocab_size, D, b->input_ids, R, ws.h, D, ws.err, stream));
+  if (mm && mm->n_vision_rows > 0)
+    OMNI_TRY_STATUS(text_embed_gather_mm(w->embed_tokens, w->vocab_size, D, b->input_ids, mm->vision_rows, mm->n_vision_rows,
+                                         mm->vision_row_of, R, ws.h, D, ws.err, stream));
+  else
+    OMNI_TRY_STATUS(text_embed_gather(w->embed_tokens, w->vocab_size, D, b->input_ids, R, ws.h, D, ws.err, stream));
   const float sm_scale = 1.0f / sqrtf((float)TEXT_HEAD);
   for (int l = 0; l < w->num_layers; ++l) {
     const omni_text_layer_weights& L = w->layers[l];
@@ -270,7 +387,11 @@ int text_forward(const omni_text_weights* w, const omni_text_batch* b, omni_stre
     }
     // (q is not pre-scaled as the DiT path does it: the general attention kernel multiplies the fp32 scores by softmax_scale *
     // log2(e) either way, so a scale folded into q would save nothing and 1 / sqrt(128), no power of two, would add a rounding)
-    OMNI_TRY_STATUS(text_rope_neox(ws.qkv, Nqkv, R, H, Hkv, w->rope_cos, w->rope_sin, w->rope_npos, b->row_pos, ws.err, stream));
+    if (mm)
+      OMNI_TRY_STATUS(text_mrope(ws.qkv, Nqkv, R, H, Hkv, w->rope_cos, w->rope_sin, w->rope_npos, mm->row_pos3, mm->section, ws.err,
+                                 stream));
+    else
+      OMNI_TRY_STATUS(text_rope_neox(ws.qkv, Nqkv, R, H, Hkv, w->rope_cos, w->rope_sin, w->rope_npos, b->row_pos, ws.err, stream));
     {
       omni_attn_params ap = {};
       ap.q = ws.qkv; ap.k = ws.qkv + Nq; ap.v = ws.qkv + Nq + Hkv * TEXT_HEAD; ap.out = ws.attn;
@@ -299,6 +420,21 @@ int text_forward(const omni_text_weights* w, const omni_text_batch* b, omni_stre
   return omni_rmsnorm(ws.h, D, b->out, D, R, D, w->final_norm_w, w->rms_norm_eps, stream);
 }
 
+int text_forward(const omni_text_weights* w, const omni_text_batch* b, omni_stream stream) {
+  if (!b) return OMNI_ERR_BAD_ARG;
+  return text_forward_impl(w, b, nullptr, stream);
+}
+
+int text_forward_mm(const omni_text_weights* w, const omni_text_batch_mm* b, omni_stream stream) {
+  if (!b) return OMNI_ERR_BAD_ARG;
+  omni_text_batch base = {};
+  base.n_prompts = b->n_prompts; base.total_rows = b->total_rows; base.max_seqlen = b->max_seqlen;
+  base.input_ids = b->input_ids; base.cu_seqlens = b->cu_seqlens; base.out = b->out;
+  base.workspace = b->workspace; base.workspace_bytes = b->workspace_bytes;
+  const TextMm mm = {b->row_pos3, b->mrope_section, b->vision_rows, b->vision_row_of, b->n_vision_rows};
+  return text_forward_impl(w, &base, &mm, stream);
+}
+
 }  // namespace
 
 // exported as const pointers, not as functions: see the header (the exported functions of ABI v14 are fixed).  Host pass only:
@@ -308,6 +444,9 @@ extern "C" int (*const omni_qwen2_text_forward)(const omni_text_weights*, const 
 extern "C" size_t (*const omni_qwen2_text_workspace_bytes)(const omni_text_weights*, int32_t) = text_workspace_bytes;
 extern "C" int (*const omni_text_rope_neox)(omni_bf16*, int64_t, int32_t, int32_t, int32_t, const float*, const float*, int32_t,
                                             const int32_t*, int32_t*, omni_stream) = text_rope_neox;
+extern "C" int (*const omni_qwen2_text_forward_mm)(const omni_text_weights*, const omni_text_batch_mm*, omni_stream) = text_forward_mm;
+extern "C" int (*const omni_text_mrope)(omni_bf16*, int64_t, int32_t, int32_t, int32_t, const float*, const float*, int32_t,
+                                        const int32_t*, const int32_t*, int32_t*, omni_stream) = text_mrope;
 extern "C" int (*const omni_text_swiglu)(const omni_bf16*, int64_t, omni_bf16*, int64_t, int32_t, int32_t, int32_t,
                                          omni_stream) = text_swiglu;
 extern "C" int (*const omni_text_embed_gather)(const omni_bf16*, int32_t, int32_t, const int32_t*, int32_t, omni_bf16*, int64_t,

@@ -154,7 +154,12 @@ class OmniDiffusionConfig:
     native_text_encoder: bool = False  # NEW, opt-in: `load_text_encoder` builds the Qwen2.5-VL prompt encoder on this library
                                      # (NativeQwenPromptEncoder: all decoder layers in one omni_qwen2_text_forward over the packed
                                      # tokens) instead of HF eager.  Text-to-image only: the Edit / Edit-Plus / Layered pipelines
-                                     # need the HF model's vision tower / caption path and refuse the flag at construction
+                                     # encode through the vision tower / caption path and refuse the flag at construction
+    native_vl_encoder: bool = False  # NEW, opt-in: the Edit / Edit-Plus pipelines' `load_text_encoder` builds the prompt encoder
+                                     # WITH pictures on this library (NativeQwenEditPromptEncoder: the vision tower in one
+                                     # omni_qwen2_vision_forward, the language model with M-RoPE in one omni_qwen2_text_forward_mm)
+                                     # instead of HF eager.  The text-to-image pipeline (its flag is native_text_encoder) and the
+                                     # Layered pipeline (its caption path generates tokens) refuse it at construction
     max_step_tokens: int | None = None  # NEW: admission bound next to max_step_batch — the largest sum of image rows x CFG
                                      # branches one forward may hold (the oldest sample always runs, alone if need be)
     # ---- the reference's remaining fields (data.py:255-360), so that a config written for it constructs here unchanged.

@@ -9,7 +9,8 @@ Same transformer as text-to-image; what changes:
     `latents.size(1)` tokens (:632);
   * everything else — true-CFG, Flow-Match Euler, decode — is the text-to-image loop.
 Prompt encoding for Edit runs the Qwen2.5-VL VISION tower on the image as well (:306-397): `text_encoder` is a
-`QwenEditPromptEncoder` (text_encoder.py: HF Qwen2_5_VLForConditionalGeneration + the checkpoint's Qwen2VLProcessor); a request
+`QwenEditPromptEncoder` (text_encoder.py: HF Qwen2_5_VLForConditionalGeneration + the checkpoint's Qwen2VLProcessor) or, with
+`OmniDiffusionConfig.native_vl_encoder`, a `NativeQwenEditPromptEncoder` (the same towers on this library's kernels); a request
 with `prompt` and no `prompt_embeds` is encoded from the prompt AND the picture — `req.extra["prompt_image"]` (PIL / array /
 tensor; what the reference calls `prompt_image`, the resized input, :686-700) or, by default, the condition image itself.
 Requests may still carry `prompt_embeds`.  The image is passed as `req.extra["image"]`
@@ -38,7 +39,8 @@ class QwenImageEditPipeline(QwenImagePipeline):
         dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
         if getattr(od_config, "native_text_encoder", False):
             raise NotImplementedError(f"{type(self).__name__}: native_text_encoder=True covers text-only prompts; this pipeline's "
-                                      "prompts go through the HF model's vision tower / caption path - leave the flag off")
+                                      "prompts go through the vision tower / caption path - leave the flag off (the Edit and "
+                                      "Edit-Plus flag for prompts with pictures is native_vl_encoder)")
         super().__init__(od_config=od_config, prefix=prefix, device=dev, transformer=transformer,
                          vae=vae if vae is not None else AutoencoderKLQwenImage(device=dev, with_encoder=True), **kw)
         if not getattr(self.vae, "with_encoder", False):
@@ -68,9 +70,17 @@ class QwenImageEditPipeline(QwenImagePipeline):
             raise FileNotFoundError(f"{model_dir!r} has no text_encoder/ + processor/ folders")
         dev = torch.device(device if device is not None else self.device)
         model = Qwen2_5_VLForConditionalGeneration.from_pretrained(te_dir, torch_dtype=BF16, local_files_only=True).to(dev).eval()
-        self.text_encoder = QwenEditPromptEncoder(model, AutoProcessor.from_pretrained(pr_dir, local_files_only=True), dtype=BF16,
-                                                  multi_image=self._multi_image_prompt)
+        processor = AutoProcessor.from_pretrained(pr_dir, local_files_only=True)
+        if getattr(self.od_config, "native_vl_encoder", False):
+            # vision tower + language model on this library's kernels; the HF blocks are dropped as their fused copies exist
+            from .text_encoder import NativeQwenEditPromptEncoder
 
+            self.text_encoder = NativeQwenEditPromptEncoder.from_hf(model, processor, multi_image=self._multi_image_prompt,
+                                                                    free_source=True)
+        else:
+            self.text_encoder = QwenEditPromptEncoder(model, processor, dtype=BF16, multi_image=self._multi_image_prompt)
+
+    _takes_native_vl_encoder = True
     _multi_image_prompt = False          # Edit-Plus numbers its pictures in the prompt ("Picture 1: ...")
     _prompt_images = None                # set for the duration of one resolve_request
 

@@ -68,6 +68,9 @@ def get_qwen_image_layered_pre_process_func(od_config=None):
 
 class QwenImageLayeredPipeline(QwenImageEditPipeline):
     DEFAULT_LAYERS = 4
+    _takes_native_vl_encoder = False
+    _native_vl_encoder_hint = ("the Layered prompt is text only and its auto-caption GENERATES tokens through the HF model, which "
+                               "the native encoder does not do - leave the flag off")
 
     def __init__(self, *, od_config=None, prefix: str = "", device=None, transformer=None, vae=None, **kw):
         tk = dict(kw.pop("transformer_kwargs", None) or {})

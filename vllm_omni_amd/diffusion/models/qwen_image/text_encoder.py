@@ -11,7 +11,9 @@ signature (`ByteTokenizer`); with a real checkpoint pass `Qwen2Tokenizer` and th
 
 Opt-in (`OmniDiffusionConfig.native_text_encoder`): `NativeQwenPromptEncoder` runs the same text model on this library - all
 decoder layers in one `omni_qwen2_text_forward` over the packed valid tokens - with the same tokenizer, template, drop index,
-outputs and mask (text-only prompts; the Edit encoders below stay on HF)."""
+outputs and mask (text-only prompts).  Opt-in (`OmniDiffusionConfig.native_vl_encoder`): `NativeQwenEditPromptEncoder` does the
+same for the Edit pipelines' prompts WITH pictures - the vision tower in one `omni_qwen2_vision_forward`, the language model with
+real M-RoPE and the image embeddings in the token rows in one `omni_qwen2_text_forward_mm`; the HF Edit encoder stays the default."""
 from __future__ import annotations
 
 import torch
@@ -189,7 +191,7 @@ class NativeQwenPromptEncoder:
 
     def __init__(self, geometry: dict, embed_tokens, final_norm_w, layers: list[dict], tokenizer, dtype=torch.bfloat16,
                  tokenizer_max_length: int = 1024, template: str = PROMPT_TEMPLATE_ENCODE, drop_idx: int | None = None,
-                 w_k32_blocked: bool = True):
+                 w_k32_blocked: bool = True, rope_npos: int | None = None):
         from .... import _native as N
 
         if not N.features() & N.FEATURE_TEXT_ENCODER:
@@ -206,7 +208,7 @@ class NativeQwenPromptEncoder:
             drop_idx = tokenizer.template_prefix_tokens(template) if hasattr(tokenizer, "template_prefix_tokens") \
                 else PROMPT_TEMPLATE_ENCODE_START_IDX
         self.prompt_template_encode_start_idx = drop_idx
-        self.rope_npos = max(2048, tokenizer_max_length + drop_idx)
+        self.rope_npos = int(rope_npos) if rope_npos else max(2048, tokenizer_max_length + drop_idx)
         self.rope_cos, self.rope_sin = text_rope_tables(geometry["theta"], self.rope_npos, device=embed_tokens.device)
         self.ones = torch.ones(geometry["hidden"], dtype=torch.bfloat16, device=embed_tokens.device)
         self._desc = self._layer_array = self._workspace = None
@@ -398,4 +400,402 @@ class QwenEditPromptEncoder:
             kw = dict(pixel_values=inputs.pixel_values, image_grid_thw=inputs.image_grid_thw)
         out = self.model(input_ids=inputs.input_ids, attention_mask=inputs.attention_mask, output_hidden_states=True, **kw)
         emb, msk = masked_drop_pad(out.hidden_states[-1], inputs.attention_mask, self.prompt_template_encode_start_idx)
+        return emb.to(device=dev, dtype=dtype or self.dtype), msk.to(dev)
+
+
+# ---- the native Edit prompt encoder: vision tower + language model with M-RoPE on this library ---------------------------------
+VISION_HEAD_PAD = 128              # the head size the vision q / k / v are zero-padded to (the attention kernel's)
+VISION_ROPE_THETA = 10000.0        # Qwen2_5_VisionRotaryEmbedding's default; the config carries no other
+EDIT_ROPE_NPOS = 8192              # rows of the language model's RoPE table: 1024 text tokens + 64 + the picture tokens fit
+
+
+def _pad_to(n: int, m: int = 64) -> int:
+    return (n + m - 1) // m * m
+
+
+def vision_model_of(model):
+    """The vision tower inside what the Edit pipelines load (`.model.visual` / `.visual` of a
+    `Qwen2_5_VLForConditionalGeneration`)."""
+    for path in (("model", "visual"), ("visual",)):
+        m = model
+        for a in path:
+            m = getattr(m, a, None)
+            if m is None:
+                break
+        if m is not None and hasattr(m, "blocks") and hasattr(m, "merger") and hasattr(m, "patch_embed"):
+            return m
+    raise TypeError(f"{type(model).__name__} holds no Qwen2.5-VL vision tower (patch_embed / blocks / merger)")
+
+
+def check_vision_geometry(vcfg, text_hidden: int | None = None) -> dict:
+    """The geometry of an HF vision config as omni_qwen2_vision_forward needs it, or ValueError naming what it does not take."""
+    hidden, heads, inter = int(vcfg.hidden_size), int(vcfg.num_heads), int(vcfg.intermediate_size)
+    head = hidden // heads
+    out = int(vcfg.out_hidden_size)
+    merge, patch, tps, cin = int(vcfg.spatial_merge_size), int(vcfg.patch_size), int(vcfg.temporal_patch_size), int(vcfg.in_channels)
+    window = int(vcfg.window_size)
+    why = None
+    if hidden % heads:
+        why = f"hidden size {hidden} over {heads} heads: not a whole head size"
+    elif head % 16 or head > VISION_HEAD_PAD:
+        why = f"vision head size {head}: the RoPE + padding kernel takes multiples of 16 up to {VISION_HEAD_PAD}"
+    elif hidden % 64 or hidden > 8192 or out % 64:
+        why = f"vision hidden size {hidden} / output size {out}: both must be multiples of 64, hidden at most 8192"
+    elif getattr(vcfg, "hidden_act", "silu") != "silu":
+        why = f"vision activation {vcfg.hidden_act!r}: the MLP kernel is SwiGLU"
+    elif merge != 2:
+        why = f"spatial merge size {merge}: the merger is built for 2 x 2 units of four consecutive rows"
+    elif window % (merge * patch) or window < merge * patch:
+        why = f"window size {window}: not a whole number of {merge * patch}-pixel merge units"
+    elif text_hidden is not None and out != text_hidden:
+        why = f"vision output size {out} is not the language model's hidden size {text_hidden}"
+    if why:
+        raise ValueError(f"the native Qwen2.5-VL Edit prompt encoder does not take this vision tower - {why}")
+    return dict(hidden=hidden, heads=heads, head=head, inter=inter, inter_pad=_pad_to(inter), out=out, merge=merge, patch=patch,
+                window=window, patch_k=cin * tps * patch * patch, patch_k_pad=_pad_to(cin * tps * patch * patch),
+                layers=int(vcfg.depth), full=sorted(int(i) for i in vcfg.fullatt_block_indexes), eps=1e-6)
+
+
+def check_mrope_section(cfg) -> list[int]:
+    rope = dict(getattr(cfg, "rope_parameters", None) or getattr(cfg, "rope_scaling", None) or {})
+    sec = [int(v) for v in (rope.get("mrope_section") or [])]
+    if len(sec) != 3 or sum(sec) != TEXT_HEAD_SIZE // 2 or any(v % 8 or v < 0 for v in sec):
+        raise ValueError(f"the native Qwen2.5-VL Edit prompt encoder does not take this text model - mrope_section {sec}: three "
+                         f"multiples of 8 that sum to {TEXT_HEAD_SIZE // 2} (the checkpoints have [16, 24, 24])")
+    return sec
+
+
+def _grids(grid_thw) -> list[tuple[int, int, int]]:
+    g = grid_thw.tolist() if isinstance(grid_thw, torch.Tensor) else grid_thw
+    return [(int(t), int(h), int(w)) for t, h, w in g]
+
+
+def check_picture_grids(grid_thw, merge: int = 2) -> list[tuple[int, int, int]]:
+    grids = _grids(grid_thw)
+    for t, h, w in grids:
+        if t != 1:
+            raise ValueError(f"a temporal grid of {t}: the native Edit prompt encoder takes still pictures (t = 1), not videos")
+        if h <= 0 or w <= 0 or h % merge or w % merge:
+            raise ValueError(f"a patch grid of {h} x {w}: both sides must be positive multiples of the merge size {merge}")
+    return grids
+
+
+def vision_window_index(grid_thw, merge: int, window_size: int, patch: int):
+    """(window_index long [rows / merge^2], cu_window int32 [n_windows + 1]): HF `get_vision_window_index` - the order of the
+    merge units in which every attention window is contiguous, and the windows' prefix sums in PATCH rows with empty windows
+    (consecutive duplicates) removed."""
+    side, unit = window_size // merge // patch, merge * merge
+    index, cu, base = [], [0], 0
+    for t, h, w in _grids(grid_thw):
+        gh, gw = h // merge, w // merge
+        idx = torch.arange(t * gh * gw).reshape(t, gh, gw)
+        ph, pw = side - gh % side, side - gw % side               # (HF pads a whole extra window when the side divides)
+        nh, nw = (gh + ph) // side, (gw + pw) // side
+        pad = torch.nn.functional.pad(idx, (0, pw, 0, ph), "constant", -100)
+        pad = pad.reshape(t, nh, side, nw, side).permute(0, 1, 3, 2, 4).reshape(t, nh * nw, side, side)
+        lens = (pad != -100).sum([2, 3]).reshape(-1)
+        flat = pad.reshape(-1)
+        index.append(flat[flat != -100] + base)
+        cu.extend((lens.cumsum(0) * unit + cu[-1]).tolist())
+        base += t * gh * gw
+    cu = torch.unique_consecutive(torch.tensor(cu, dtype=torch.int32))
+    return torch.cat(index), cu
+
+
+def vision_row_order(window_index: torch.Tensor, unit: int = 4) -> torch.Tensor:
+    """The permutation of the processor's PATCH rows into window order: merge unit u holds rows unit * u .. unit * u + unit - 1."""
+    return (window_index[:, None] * unit + torch.arange(unit)[None, :]).reshape(-1)
+
+
+def vision_cu_image(grid_thw) -> torch.Tensor:
+    """int32 [n + 1] prefix sums of the pictures' patch rows (one attention segment per frame: HF `get_vision_cu_seqlens`)."""
+    lens = [h * w for t, h, w in _grids(grid_thw) for _ in range(t)]
+    return torch.tensor([0] + lens, dtype=torch.int32).cumsum(0).to(torch.int32)
+
+
+def vision_patch_positions(grid_thw, merge: int) -> torch.Tensor:
+    """long [rows, 2]: the (h, w) grid position of every patch row in the processor's order (merge-block major): HF
+    `get_vision_position_ids`."""
+    out = []
+    for t, h, w in _grids(grid_thw):
+        hp, wp = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
+        shape = (h // merge, merge, w // merge, merge)
+        hp, wp = hp.reshape(shape).transpose(1, 2).flatten(), wp.reshape(shape).transpose(1, 2).flatten()
+        out.append(torch.stack([hp, wp], dim=-1).repeat(t, 1))
+    return torch.cat(out)
+
+
+def vision_rope_tables(pos_hw: torch.Tensor, head: int, theta: float = VISION_ROPE_THETA):
+    """fp32 cos / sin [rows, head / 2] as `Qwen2_5_VisionRotaryEmbedding` + the tower's forward compute them: head / 4
+    frequencies theta^(-2 i / (head / 2)), the first head / 4 columns turn with the row's h, the rest with its w; HF then repeats
+    the head / 2 columns for the second half of the head, which the kernel does by addressing."""
+    dim = head // 2
+    inv = 1.0 / (theta ** (torch.arange(0, dim, 2, dtype=torch.float) / dim))
+    ang = (pos_hw.unsqueeze(-1) * inv).flatten(1)
+    return ang.cos().contiguous(), ang.sin().contiguous()
+
+
+def mrope_positions(ids: torch.Tensor, lens: list[int], image_token_id: int, grid_thw, merge: int = 2) -> torch.Tensor:
+    """int32 [3, sum(lens)]: Qwen2.5-VL's 3-D token positions (`Qwen2_5_VLModel.get_rope_index`) of the packed valid tokens.  Text
+    runs count on in all three rows; a run of picture tokens takes the next grid: temporal = the run's start, height / width =
+    start + the merged row / column; the count then moves on by max(h, w) / merge."""
+    grids = iter(_grids(grid_thw))
+    out = []
+    for row in torch.split(ids, lens):
+        is_img = (row == image_token_id).tolist()
+        cur, i, parts = 0, 0, []
+        while i < len(is_img):
+            j = i
+            while j < len(is_img) and is_img[j] == is_img[i]:
+                j += 1
+            if not is_img[i]:
+                parts.append(torch.arange(j - i).view(1, -1).expand(3, -1) + cur)
+                cur += j - i
+            else:
+                try:
+                    t, h, w = next(grids)
+                except StopIteration:
+                    raise ValueError("more runs of picture tokens than pictures") from None
+                gh, gw = h // merge, w // merge
+                if j - i != t * gh * gw:
+                    raise ValueError(f"a run of {j - i} picture tokens for a picture of {t * gh * gw} merged patches")
+                tt, hh, ww = torch.meshgrid(torch.arange(t), torch.arange(gh) + cur, torch.arange(gw) + cur, indexing="ij")
+                parts.append(torch.stack([tt + cur, hh, ww]).reshape(3, -1))
+                cur += max(h, w) // merge
+            i = j
+        out.append(torch.cat(parts, dim=1) if parts else torch.zeros(3, 0, dtype=torch.long))
+    if next(grids, None) is not None:
+        raise ValueError("more pictures than runs of picture tokens")
+    return torch.cat(out, dim=1).to(torch.int32).contiguous()
+
+
+def vision_row_map(ids: torch.Tensor, image_token_id: int, window_index: torch.Tensor | None) -> torch.Tensor:
+    """int32 [rows]: for every packed token the row of the tower's WINDOW-ORDER output it takes (-1: its token embedding).  HF
+    scatters merger output k (in the processor's order) into the k-th picture token; output k sits at row argsort(window_index)[k]
+    of the window-order result, so the reverse permutation is folded into the map."""
+    img = ids == image_token_id
+    out = torch.full((ids.numel(),), -1, dtype=torch.int32)
+    n = int(img.sum())
+    have = 0 if window_index is None else window_index.numel()
+    if n != have:
+        raise ValueError(f"{n} picture tokens in the prompt for {have} merged patch rows of the pictures")
+    if n:
+        out[img] = torch.argsort(window_index).to(torch.int32)
+    return out
+
+
+def pad_vision_block(blk, g: dict) -> dict:
+    """One HF vision block's tensors as omni_vision_layer_weights wants them (bf16, row-major, zero-padded - all exact): the
+    projection's input columns from `head` to 128 per head, the intermediate size to a multiple of 64 in gate | up (rows, bias)
+    and down (columns)."""
+    bf = lambda t: t.detach().to(torch.bfloat16)
+    D, H, hd, I, Ip = g["hidden"], g["heads"], g["head"], g["inter"], g["inter_pad"]
+    a, m = blk.attn, blk.mlp
+    proj = bf(a.proj.weight).new_zeros(D, H, VISION_HEAD_PAD)
+    proj[:, :, :hd] = bf(a.proj.weight).view(D, H, hd)
+    gu_w = proj.new_zeros(2 * Ip, D)
+    gu_w[:I], gu_w[Ip:Ip + I] = bf(m.gate_proj.weight), bf(m.up_proj.weight)
+    gu_b = proj.new_zeros(2 * Ip)
+    gu_b[:I], gu_b[Ip:Ip + I] = bf(m.gate_proj.bias), bf(m.up_proj.bias)
+    down = proj.new_zeros(D, Ip)
+    down[:, :I] = bf(m.down_proj.weight)
+    return dict(norm1_w=bf(blk.norm1.weight).contiguous(), qkv_w=bf(a.qkv.weight).contiguous(), qkv_b=bf(a.qkv.bias).contiguous(),
+                proj_w=proj.view(D, H * VISION_HEAD_PAD), proj_b=bf(a.proj.bias).contiguous(),
+                norm2_w=bf(blk.norm2.weight).contiguous(), gate_up_w=gu_w, gate_up_b=gu_b, down_w=down,
+                down_b=bf(m.down_proj.bias).contiguous())
+
+
+_VISION_MATRICES = ("qkv_w", "proj_w", "gate_up_w", "down_w")
+
+
+class NativeQwenEditPromptEncoder:
+    """`QwenEditPromptEncoder` on this library: same processor, templates, drop index 64, outputs and mask.  The vision tower runs
+    as ONE omni_qwen2_vision_forward over the patch rows of all pictures in window order, the language model as ONE
+    omni_qwen2_text_forward_mm over the packed valid tokens, with Qwen2.5-VL's 3-D positions (`get_rope_index`) and the image
+    embeddings gathered into the picture tokens' rows.  Built by `from_hf`; anything the kernels do not take raises ValueError
+    there (or, for an input such as a video, at the call) - there is no fall-back to the HF model.
+    The vision result of the last picture set is kept: a request's negative prompt reuses its positive prompt's vision forward."""
+
+    def __init__(self, text: "NativeQwenPromptEncoder", vgeom: dict, vweights: dict, vlayers: list[dict], processor,
+                 image_token_id: int, mrope_section: list[int], video_token_id: int | None = None, multi_image: bool = False,
+                 template: str | None = None, drop_idx: int = EDIT_PROMPT_TEMPLATE_ENCODE_START_IDX, dtype=torch.bfloat16,
+                 w_k32_blocked: bool = True):
+        from .... import _native as N
+
+        if not N.features() & N.FEATURE_VISION_ENCODER:
+            raise N.OmniNativeError("this libomni_cdna4.so does not report OMNI_FEATURE_VISION_ENCODER: it has no "
+                                    "omni_qwen2_vision_forward / omni_qwen2_text_forward_mm - rebuild it (python "
+                                    "vllm_omni_amd/csrc/build.py); the native Edit prompt encoder never falls back to the HF model")
+        if dtype != torch.bfloat16:
+            raise ValueError(f"the native Edit prompt encoder computes in bfloat16, not {dtype}")
+        self.text, self.vgeom, self.vweights, self.vlayers = text, vgeom, vweights, vlayers
+        self.processor, self.dtype, self.multi_image = processor, dtype, multi_image
+        self.image_token_id, self.video_token_id, self.mrope_section = int(image_token_id), video_token_id, list(mrope_section)
+        self.prompt_template_encode = template or (EDIT_PLUS_PROMPT_TEMPLATE_ENCODE if multi_image else EDIT_PROMPT_TEMPLATE_ENCODE)
+        self.prompt_template_encode_start_idx = drop_idx
+        self.tokenizer_max_length = 1024
+        self.w_k32_blocked = bool(w_k32_blocked)
+        self.vones = torch.ones(vgeom["hidden"], dtype=torch.bfloat16, device=vweights["patch_w"].device)
+        self._vdesc = self._vlayer_array = self._vworkspace = None
+        self._vision_cache = None          # (grids, pixel_values on the host, window-order output on the device, window_index)
+
+    @classmethod
+    def from_hf(cls, vl_model, processor, multi_image: bool = False, free_source: bool = False, **kw):
+        """From an HF `Qwen2_5_VLForConditionalGeneration`, on the device its weights are on: the vision and text weights are
+        fused and zero-padded once (K32-blocked unless `w_k32_blocked=False`).  `free_source`: every HF block / decoder layer is
+        dropped as soon as its copy exists (the HF model cannot run afterwards)."""
+        from .... import ops
+
+        vis, tm = vision_model_of(vl_model), text_model_of(vl_model)
+        cfg = vl_model.config
+        vcfg = getattr(cfg, "vision_config", None) or vis.config
+        tg = check_text_geometry(tm.config)                        # refusals first: nothing is touched before all of them passed
+        sec = check_mrope_section(tm.config)
+        g = check_vision_geometry(vcfg, tg["hidden"])
+        if len(vis.blocks) != g["layers"]:
+            raise ValueError(f"the vision tower has {len(vis.blocks)} blocks, its config says {g['layers']}")
+        blocked = bool(kw.get("w_k32_blocked", True))
+        bf = lambda t: t.detach().to(torch.bfloat16).contiguous()
+        mat = (lambda t: ops.w_to_k32_blocked(t.contiguous())) if blocked else (lambda t: t.contiguous())
+        D = g["hidden"]
+        pw = bf(vis.patch_embed.proj.weight).reshape(D, -1)
+        if pw.shape[1] != g["patch_k"]:
+            raise ValueError(f"the patch embedding has {pw.shape[1]} inputs per patch, its config says {g['patch_k']}")
+        patch_w = pw.new_zeros(D, g["patch_k_pad"])
+        patch_w[:, :g["patch_k"]] = pw
+        mg = vis.merger
+        vweights = dict(patch_w=mat(patch_w), merger_norm_w=bf(mg.ln_q.weight), merger_fc1_w=mat(bf(mg.mlp[0].weight)),
+                        merger_fc1_b=bf(mg.mlp[0].bias), merger_fc2_w=mat(bf(mg.mlp[2].weight)), merger_fc2_b=bf(mg.mlp[2].bias))
+        vlayers = []
+        for i in range(len(vis.blocks)):
+            L = pad_vision_block(vis.blocks[i], g)
+            for n in _VISION_MATRICES:
+                L[n] = mat(L[n])
+            L["full_attention"] = int(i in g["full"])
+            vlayers.append(L)
+            if free_source:
+                vis.blocks[i] = torch.nn.Identity()
+        if free_source:
+            vis.blocks = torch.nn.ModuleList()
+        text = NativeQwenPromptEncoder.from_hf(tm, None, free_source=free_source, drop_idx=EDIT_PROMPT_TEMPLATE_ENCODE_START_IDX,
+                                               rope_npos=EDIT_ROPE_NPOS, w_k32_blocked=blocked)
+        return cls(text, g, vweights, vlayers, processor, cfg.image_token_id, sec, video_token_id=getattr(cfg, "video_token_id", None),
+                   multi_image=multi_image, **kw)
+
+    def _vision_descriptor(self):
+        if self._vdesc is None:
+            from .... import _native as N
+            from ....ops import _p
+
+            g = self.vgeom
+            arr = (N.VisionLayerWeights * len(self.vlayers))()
+            for rec, L in zip(arr, self.vlayers):
+                for name, _ in N.VisionLayerWeights._fields_:
+                    if name == "full_attention":
+                        rec.full_attention = L[name]
+                    elif name != "reserved":
+                        setattr(rec, name, _p(L[name], name=name))
+            w = N.VisionWeights()
+            w.num_layers, w.hidden_size, w.num_heads, w.head_dim = len(self.vlayers), g["hidden"], g["heads"], g["head"]
+            w.intermediate_size, w.patch_k, w.out_hidden_size = g["inter_pad"], g["patch_k_pad"], g["out"]
+            w.gemm_w_k32_blocked, w.rms_norm_eps = int(self.w_k32_blocked), g["eps"]
+            for name, t in self.vweights.items():
+                setattr(w, name, _p(t, name=name))
+            w.ones = _p(self.vones, name="ones")
+            w.layers = arr
+            self._vdesc, self._vlayer_array = w, arr
+        return self._vdesc
+
+    @torch.no_grad()
+    def vision_forward(self, pixel_values: torch.Tensor, grid_thw):
+        """The processor's `pixel_values` [rows, 1176] and `image_grid_thw` -> (the merger's output in WINDOW order
+        [rows / 4, out] bf16 on the device, window_index).  HF's order is `out[argsort(window_index)]`."""
+        from .... import ops
+
+        g = self.vgeom
+        grids = check_picture_grids(grid_thw, g["merge"])
+        px = pixel_values.detach().cpu()
+        if px.dim() != 2 or px.shape[1] != g["patch_k"] or px.shape[0] != sum(t * h * w for t, h, w in grids):
+            raise ValueError(f"pixel_values of shape {tuple(px.shape)} for grids {grids} and {g['patch_k']} values per patch")
+        c = self._vision_cache
+        if c is not None and c[0] == grids and c[1].shape == px.shape and c[1].dtype == px.dtype and torch.equal(c[1], px):
+            return c[2], c[3]
+        dev = self.vones.device
+        window_index, cu_window = vision_window_index(grids, g["merge"], g["window"], g["patch"])
+        order = vision_row_order(window_index, g["merge"] ** 2)
+        cu_image = vision_cu_image(grids)
+        cos, sin = vision_rope_tables(vision_patch_positions(grids, g["merge"])[order], g["head"])
+        pixels = torch.zeros(px.shape[0], g["patch_k_pad"], dtype=torch.bfloat16)
+        pixels[:, :g["patch_k"]] = px[order].to(torch.bfloat16)      # (HF casts the fp32 pixels to the tower's dtype as well)
+        cu = torch.cat([cu_window, cu_image]).to(dev)
+        tabs = torch.cat([cos, sin]).to(dev)
+        w = self._vision_descriptor()
+        need = ops.qwen2_vision_workspace_bytes(w, px.shape[0])
+        if self._vworkspace is None or self._vworkspace.numel() < need:
+            self._vworkspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = ops.qwen2_vision_forward(w, pixels.to(dev), cu[:cu_window.numel()], cu[cu_window.numel():],
+                                       int((cu_window[1:] - cu_window[:-1]).max()), int((cu_image[1:] - cu_image[:-1]).max()),
+                                       tabs[:cos.shape[0]], tabs[cos.shape[0]:], self._vworkspace)
+        self._vision_cache = (grids, px.clone(), out, window_index)
+        return out, window_index
+
+    @torch.no_grad()
+    def get_image_features(self, pixel_values, grid_thw) -> torch.Tensor:
+        """The merger's output in the processor's (HF's) order: what `Qwen2_5_VLModel.get_image_features` concatenates."""
+        out, window_index = self.vision_forward(pixel_values, grid_thw)
+        return out[torch.argsort(window_index).to(out.device)]
+
+    @torch.no_grad()
+    def encode_packed(self, ids, cu_seqlens, row_pos3, max_seqlen: int, vision_rows=None, vision_row_of=None) -> torch.Tensor:
+        """Packed int32 tokens, their [3, rows] positions and the vision rows (all on the weights' device) -> last hidden state."""
+        from .... import ops
+
+        w = self.text._descriptor()
+        need = ops.qwen2_text_workspace_bytes(w, ids.numel())
+        if self.text._workspace is None or self.text._workspace.numel() < need:
+            self.text._workspace = torch.zeros(need, dtype=torch.uint8, device=ids.device)   # zeroed: the error word in front
+        return ops.qwen2_text_forward_mm(w, ids, cu_seqlens, row_pos3, self.mrope_section, max_seqlen, self.text._workspace,
+                                         vision_rows=vision_rows, vision_row_of=vision_row_of)
+
+    @torch.no_grad()
+    def get_qwen_prompt_embeds(self, prompt, image=None, device=None, dtype=None):
+        prompt = [prompt] if isinstance(prompt, str) else list(prompt)
+        wdev = self.text.embed_tokens.device
+        dev = device if device is not None else wdev
+        drop = self.prompt_template_encode_start_idx
+        if isinstance(image, (list, tuple)):
+            image = [to_processor_image(im) for im in image]
+        elif image is not None:
+            image = to_processor_image(image)
+        if self.multi_image:
+            n = len(image) if isinstance(image, list) else (0 if image is None else 1)
+            base = "".join(EDIT_PLUS_IMG_PROMPT.format(i + 1) for i in range(n))
+            txt = [self.prompt_template_encode.format(base + e) for e in prompt]
+        else:
+            txt = [self.prompt_template_encode.format(e) for e in prompt]
+        inputs = self.processor(text=txt, images=image, padding=True, return_tensors="pt")
+        if getattr(inputs, "pixel_values_videos", None) is not None or getattr(inputs, "video_grid_thw", None) is not None:
+            raise ValueError("video inputs: the native Edit prompt encoder takes still pictures only")
+        ids, cu, _, lens = pack_tokens(inputs.input_ids.cpu(), inputs.attention_mask.cpu())
+        if len(lens) > MAX_PROMPTS_PER_FORWARD:
+            raise ValueError(f"{len(lens)} prompts in one call: at most {MAX_PROMPTS_PER_FORWARD}")
+        vocab = self.text.embed_tokens.shape[0]
+        if ids.numel() == 0 or int(ids.min()) < 0 or int(ids.max()) >= vocab:
+            raise ValueError(f"token ids outside the embedding table [0, {vocab})")
+        if self.video_token_id is not None and bool((ids == self.video_token_id).any()):
+            raise ValueError("video tokens in the prompt: the native Edit prompt encoder takes still pictures only")
+        grids, vision_rows, window_index = [], None, None
+        if getattr(inputs, "pixel_values", None) is not None:
+            grids = check_picture_grids(inputs.image_grid_thw, self.vgeom["merge"])
+            vision_rows, window_index = self.vision_forward(inputs.pixel_values, grids)
+        row_of = vision_row_map(ids, self.image_token_id, window_index)
+        pos3 = mrope_positions(ids, lens, self.image_token_id, grids, self.vgeom["merge"])
+        if int(pos3.max()) >= self.text.rope_npos:
+            raise ValueError(f"a token position of {int(pos3.max())} exceeds the RoPE table of {self.text.rope_npos} positions")
+        R, n = ids.numel(), len(lens)
+        packed = torch.cat([ids, cu, pos3.reshape(-1), row_of]).to(wdev)                    # one upload
+        hidden = self.encode_packed(packed[:R], packed[R:R + n + 1], packed[R + n + 1:4 * R + n + 1].view(3, R), max(lens),
+                                    vision_rows=vision_rows,
+                                    vision_row_of=packed[4 * R + n + 1:] if vision_rows is not None else None)
+        emb, msk = packed_drop_pad(hidden, lens, drop)
         return emb.to(device=dev, dtype=dtype or self.dtype), msk.to(dev)

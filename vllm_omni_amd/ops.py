@@ -541,6 +541,123 @@ def qwen2_text_forward(weights: "N.TextWeights", input_ids, cu_seqlens, row_pos,
     return y
 
 
+def _need_vision_encoder(what: str) -> None:
+    if not N.features() & N.FEATURE_VISION_ENCODER:
+        raise N.OmniNativeError(f"this libomni_cdna4.so does not report OMNI_FEATURE_VISION_ENCODER: it has no {what} (the native "
+                                "Qwen2.5-VL vision tower / Edit prompt encoder); there is no torch fallback")
+
+
+def vision_rope_pad(qkv, num_heads: int, head_dim: int, cos_tab, sin_tab, out=None):
+    """omni_vision_rope_pad: qkv [rows, >= 3 H hd] bf16 (q | k | v, a row stride is honoured) -> [rows, 3 H 128]: q and k rotated
+    by the per-row fp32 tables cos_tab / sin_tab [rows, hd / 2] (rotate-half, partner at + hd / 2), v copied, columns hd .. 127 of
+    every head zero.  `out` may be a wider row-strided view."""
+    _need_vision_encoder("omni_vision_rope_pad")
+    rows, _, ld = _rows2d(qkv, "qkv")
+    want = (rows, head_dim // 2)
+    if tuple(cos_tab.shape) != want or tuple(sin_tab.shape) != want or not (cos_tab.is_contiguous() and sin_tab.is_contiguous()):
+        raise N.OmniNativeError(f"vision_rope_pad: cos_tab / sin_tab are contiguous fp32 {list(want)} tables, one row per qkv row")
+    y = torch.empty(rows, 3 * num_heads * 128, dtype=BF16, device=qkv.device) if out is None else out
+    if y.shape[0] != rows:
+        raise N.OmniNativeError(f"vision_rope_pad: out has {y.shape[0]} rows for {rows}")
+    N.check(N.lib().omni_vision_rope_pad(_p(qkv, name="qkv"), ld, _p(y, name="out"), y.stride(0), rows, num_heads, head_dim,
+                                         _p(cos_tab, torch.float32, "cos"), _p(sin_tab, torch.float32, "sin"), _stream()),
+            "omni_vision_rope_pad")
+    return y
+
+
+def gelu_erf(x, out=None, *, out_k32_blocked: bool = False):
+    """omni_gelu_erf: exact-erf GELU (torch.nn.GELU()) of x [rows, n] bf16; `out=x` runs in place; out_k32_blocked: the result
+    (same shape) holds the K32-blocked order [n/32][rows][32] for a GEMM's `a_k32_blocked`."""
+    _need_vision_encoder("omni_gelu_erf")
+    rows, n, ld = _rows2d(x, "x")
+    y = torch.empty(rows, n, dtype=BF16, device=x.device) if out is None else out
+    if out_k32_blocked and not y.is_contiguous():
+        raise N.OmniNativeError("gelu_erf: a K32-blocked output is one contiguous buffer")
+    N.check(N.lib().omni_gelu_erf(_p(x, name="x"), ld, _p(y, name="out"), y.stride(0), rows, n, rows if out_k32_blocked else 0,
+                                  _stream()), "omni_gelu_erf")
+    return y
+
+
+def text_mrope_(qkv, num_heads: int, num_kv_heads: int, cos_tab, sin_tab, row_pos3, mrope_section, err=None):
+    """omni_text_mrope: `text_rope_neox_` with the three M-RoPE position rows row_pos3 int32 [3, rows] (contiguous) and
+    mrope_section (three ints that sum to 64, multiples of 8): rotary pair i reads the tables at the row of its section."""
+    _need_vision_encoder("omni_text_mrope")
+    rows, _, ld = _rows2d(qkv, "qkv")
+    if cos_tab.shape != sin_tab.shape or cos_tab.dim() != 2 or cos_tab.shape[1] != 64 or not (cos_tab.is_contiguous() and sin_tab.is_contiguous()):
+        raise N.OmniNativeError("text_mrope_: cos_tab / sin_tab are contiguous fp32 [npos, 64] tables")
+    if tuple(row_pos3.shape) != (3, rows) or not row_pos3.is_contiguous():
+        raise N.OmniNativeError(f"text_mrope_: row_pos3 must be a contiguous [3, {rows}] tensor, got {tuple(row_pos3.shape)}")
+    sec = (C.c_int32 * 3)(*[int(v) for v in mrope_section])
+    N.check(N.lib().omni_text_mrope(_p(qkv, name="qkv"), ld, rows, num_heads, num_kv_heads, _p(cos_tab, torch.float32, "cos"),
+                                    _p(sin_tab, torch.float32, "sin"), cos_tab.shape[0], _p(row_pos3, torch.int32, "row_pos3"),
+                                    sec, _p(err, torch.int32, "err"), _stream()), "omni_text_mrope")
+    return qkv
+
+
+def qwen2_vision_workspace_bytes(weights: "N.VisionWeights", rows: int) -> int:
+    _need_vision_encoder("omni_qwen2_vision_workspace_bytes")
+    return int(N.lib().omni_qwen2_vision_workspace_bytes(C.byref(weights), int(rows)))
+
+
+def qwen2_vision_forward(weights: "N.VisionWeights", pixels, cu_window, cu_image, max_window: int, max_image: int, cos_tab, sin_tab,
+                         workspace, out=None):
+    """omni_qwen2_vision_forward: the whole Qwen2.5-VL vision tower over the packed patch rows of all pictures IN WINDOW ORDER.
+    pixels [rows, patch_k] bf16 (zero-padded columns), cu_window / cu_image int32 prefix sums, cos_tab / sin_tab fp32
+    [rows, head_dim / 2], all on the device -> [rows / 4, out_hidden] bf16, still in window order."""
+    _need_vision_encoder("omni_qwen2_vision_forward")
+    rows, kp, ld = _rows2d(pixels, "pixels")
+    if ld != kp or kp != weights.patch_k:
+        raise N.OmniNativeError(f"qwen2_vision_forward: pixels must be contiguous [rows, {weights.patch_k}], got {tuple(pixels.shape)}")
+    want = (rows, weights.head_dim // 2)
+    if tuple(cos_tab.shape) != want or tuple(sin_tab.shape) != want or not (cos_tab.is_contiguous() and sin_tab.is_contiguous()):
+        raise N.OmniNativeError(f"qwen2_vision_forward: cos_tab / sin_tab are contiguous fp32 {list(want)} tables")
+    if not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise N.OmniNativeError("qwen2_vision_forward: the workspace must be a contiguous uint8 DEVICE tensor")
+    y = torch.empty(rows // 4, weights.out_hidden_size, dtype=BF16, device=pixels.device) if out is None else out
+    if not y.is_contiguous():
+        raise N.OmniNativeError("qwen2_vision_forward: out must be contiguous")
+    b = N.VisionBatch()
+    b.rows, b.n_windows, b.n_images = rows, cu_window.numel() - 1, cu_image.numel() - 1
+    b.max_window, b.max_image = int(max_window), int(max_image)
+    b.pixels, b.cu_window, b.cu_image = _p(pixels, name="pixels"), _p(cu_window, torch.int32, "cu_window"), _p(cu_image, torch.int32, "cu_image")
+    b.rope_cos, b.rope_sin, b.out = _p(cos_tab, torch.float32, "cos"), _p(sin_tab, torch.float32, "sin"), _p(y, name="out")
+    b.workspace, b.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    N.check(N.lib().omni_qwen2_vision_forward(C.byref(weights), C.byref(b), _stream()), "omni_qwen2_vision_forward")
+    return y
+
+
+def qwen2_text_forward_mm(weights: "N.TextWeights", input_ids, cu_seqlens, row_pos3, mrope_section, max_seqlen: int, workspace,
+                          vision_rows=None, vision_row_of=None, out=None):
+    """omni_qwen2_text_forward_mm: `qwen2_text_forward` with the three M-RoPE position rows row_pos3 int32 [3, rows] and, where
+    vision_row_of int32 [rows] is >= 0, vision_rows [n, hidden] bf16 in place of the token embedding (both None: text only)."""
+    _need_vision_encoder("omni_qwen2_text_forward_mm")
+    rows = input_ids.numel()
+    if tuple(row_pos3.shape) != (3, rows) or not row_pos3.is_contiguous():
+        raise N.OmniNativeError(f"qwen2_text_forward_mm: row_pos3 must be a contiguous [3, {rows}] tensor, got {tuple(row_pos3.shape)}")
+    if (vision_rows is None) != (vision_row_of is None):
+        raise N.OmniNativeError("qwen2_text_forward_mm: vision_rows and vision_row_of come together")
+    if vision_rows is not None and (vision_row_of.numel() != rows or not vision_rows.is_contiguous()
+                                    or vision_rows.dim() != 2 or vision_rows.shape[1] != weights.hidden_size):
+        raise N.OmniNativeError(f"qwen2_text_forward_mm: vision_rows is contiguous [n, {weights.hidden_size}], vision_row_of has "
+                                f"one entry per token ({rows})")
+    if not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise N.OmniNativeError("qwen2_text_forward_mm: the workspace must be a contiguous uint8 DEVICE tensor")
+    y = torch.empty(rows, weights.hidden_size, dtype=BF16, device=input_ids.device) if out is None else out
+    if not y.is_contiguous():
+        raise N.OmniNativeError("qwen2_text_forward_mm: out must be contiguous")
+    b = N.TextBatchMm()
+    b.n_prompts, b.total_rows, b.max_seqlen = cu_seqlens.numel() - 1, rows, int(max_seqlen)
+    b.input_ids, b.cu_seqlens = _p(input_ids, torch.int32, "input_ids"), _p(cu_seqlens, torch.int32, "cu_seqlens")
+    b.row_pos3, b.out = _p(row_pos3, torch.int32, "row_pos3"), _p(y, name="out")
+    b.workspace, b.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    if vision_rows is not None:
+        b.vision_rows, b.vision_row_of = _p(vision_rows, name="vision_rows"), _p(vision_row_of, torch.int32, "vision_row_of")
+        b.n_vision_rows = vision_rows.shape[0]
+    b.mrope_section = (C.c_int32 * 3)(*[int(v) for v in mrope_section])
+    N.check(N.lib().omni_qwen2_text_forward_mm(C.byref(weights), C.byref(b), _stream()), "omni_qwen2_text_forward_mm")
+    return y
+
+
 def vae_conv2d(x, w, bias=None, *, gamma=None, silu=True, res=None, upsample2x=False, downsample2x=False, clamp=None,
                out=None, x_bordered=False, y_bordered=False, norm_gamma=None, norm_silu=True, keep_raw=True):
     """NHWC bf16 conv (3x3 pad 1 or 1x1): x [B,H,W,Cin], w [Cout,ks,ks,Cin].  downsample2x: the encoder's zero-pad
