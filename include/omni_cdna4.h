@@ -58,6 +58,8 @@ const char* omni_status_string(int status);
 #define OMNI_FEATURE_TEXT_ENCODER 16u /* the library exports omni_qwen2_text_forward and its companions: function pointers */
 #define OMNI_FEATURE_VISION_ENCODER 32u /* the library exports omni_qwen2_vision_forward, omni_qwen2_text_forward_mm and their
                                         * companions: function pointers */
+#define OMNI_FEATURE_TEXT_DECODE 64u /* the library exports omni_qwen2_text_prefill, omni_qwen2_text_decode_step and their
+                                      * companions (KV-cache greedy decode of the Qwen2.5-VL text model): function pointers */
 uint32_t omni_features(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -682,6 +684,152 @@ typedef struct omni_text_batch_mm {
  * [-1, n_vision_rows) yields a ZERO row (never a read) and sets the error word.  With n_vision_rows = 0 and three equal position
  * rows the launches and the output are those of omni_qwen2_text_forward, bit for bit. */
 extern int (*const omni_qwen2_text_forward_mm)(const omni_text_weights* w, const omni_text_batch_mm* b, omni_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Greedy decode of the Qwen2.5-VL text model with a KV cache: the auto-caption of the Layered pipeline
+ * (pipeline_qwen_image_layered.py:495-513: `text_encoder.generate(**inputs, max_new_tokens=512)`), the one place where the
+ * Qwen-Image pipelines GENERATE tokens.  Optional symbols of ABI v14: ask omni_features() & OMNI_FEATURE_TEXT_DECODE; const
+ * function POINTERS like omni_qwen2_text_forward_mm, for the same reason.  No existing struct changes.
+ *
+ * A decode step streams every weight once for M = n_seq <= 8 rows: nothing of the 256-row-tile MFMA GEMM fits, so the step
+ * runs on three kernels of its own (exported on their own as well):
+ *   omni_gemv_bf16            weight-streaming GEMV family, M <= 8 rows
+ *   omni_decode_attention     one query row per sequence against the cache, split over key chunks, log-sum-exp combine
+ *   omni_text_penalized_argmax  repetition penalty + argmax + EOS test + the bookkeeping of the step
+ * ---------------------------------------------------------------------------------------------- */
+/* omni_gemv_bf16: out[m, n] = epilogue(sum_k A[m, k] W[n, k] + bias[n]), m < M <= 8, fp32 accumulation.
+ * A [M, K] bf16 row-major (lda); W [N, K] bf16 where it already lies: row-major or (w_k32_blocked = 1) K32-blocked
+ * [K/32][N][32].  Epilogues: bias (nullable); res (nullable): out = res + bf16(acc + bias) - the product is rounded to bf16,
+ * then added, as OMNI_EPI_BIAS_GATE_RES with a gate of ones does (res may alias out); out_f32 (nullable) takes the fp32 value
+ * instead of out (no res then).  Exactly one of out / out_f32.  One workgroup = 8 columns x all of K over four waves, whose
+ * partial sums meet in LDS (no fp32 round trip through HBM): ceil(N / 8) workgroups, 448 at N = 3584.
+ * Status before the launch: null A / W / output, M, N or K < 1, lda < K, ldo < N -> OMNI_ERR_BAD_ARG; M > 8, K % 32 != 0, both
+ * outputs, out_f32 with res -> OMNI_ERR_UNSUPPORTED; A or W not 16-byte aligned, lda % 8 != 0 -> OMNI_ERR_ALIGN. */
+typedef struct omni_gemv_params {
+  const omni_bf16* A;
+  int64_t lda;
+  int32_t M, N, K, w_k32_blocked;
+  const omni_bf16* W;
+  const omni_bf16* bias;   /* [N], nullable */
+  const omni_bf16* res;    /* [M, ldres], nullable */
+  int64_t ldres;
+  omni_bf16* out;          /* [M, ldo] */
+  float* out_f32;          /* [M, ldo] */
+  int64_t ldo;
+} omni_gemv_params;
+extern int (*const omni_gemv_bf16)(const omni_gemv_params* p, omni_stream stream);
+
+/* omni_decode_attention: out[s, h, :] = softmax(scale * q[s, h, :] . K[s, h / G, 0 .. n_s - 1, :]) V[...], G = H / H_kv <= 8 query
+ * heads sharing each K/V head, n_s = min(lens[s] + len_add, capacity) keys; the length is DEVICE memory (the host does not
+ * know it without a read): the grid is sized by capacity, ceil(capacity / OMNI_DECODE_ATTN_CHUNK) x H_kv x n_seq workgroups,
+ * and those whose key chunk lies behind n_s exit.  Cache rows at and behind n_s are never read.  A sequence with done[s] != 0
+ * (done nullable) or n_s < 1 is skipped: its output row is not written.
+ * k_cache / v_cache: bf16 [n_seq][H_kv][capacity][128]; q [n_seq, ldq >= H * 128]; out [n_seq, ldo >= H * 128].
+ * workspace: fp32 partial results, as many bytes as omni_decode_attention_workspace_bytes answers for n_seq, H and capacity.
+ * Status before any launch: null pointer, non-positive count, short workspace -> OMNI_ERR_BAD_ARG; head_dim != 128, n_seq > 8,
+ * H % H_kv != 0, H / H_kv > 8 -> OMNI_ERR_UNSUPPORTED; q, out, caches or workspace not 16-byte aligned, ldq % 8, ldo % 8 ->
+ * OMNI_ERR_ALIGN. */
+#define OMNI_DECODE_ATTN_CHUNK 64
+typedef struct omni_decode_attn_params {
+  const omni_bf16* q;
+  int64_t ldq;
+  const omni_bf16* k_cache;
+  const omni_bf16* v_cache;
+  omni_bf16* out;
+  int64_t ldo;
+  const int32_t* lens;     /* DEVICE [n_seq] */
+  const int32_t* done;     /* DEVICE [n_seq], nullable */
+  int32_t len_add;         /* keys = lens[s] + len_add (the decode step: cur_len + 1, the row it has just appended) */
+  int32_t n_seq, H, H_kv, head_dim, capacity;
+  float softmax_scale;
+  int32_t reserved;        /* 0 */
+  void* workspace;
+  size_t workspace_bytes;
+} omni_decode_attn_params;
+extern int (*const omni_decode_attention)(const omni_decode_attn_params* p, omni_stream stream);
+extern size_t (*const omni_decode_attention_workspace_bytes)(int32_t n_seq, int32_t H, int32_t capacity);
+
+/* The per-sequence decode control words: int32 [OMNI_DECODE_CTRL_WORDS][8] on the device, word w of sequence s at
+ * ctrl[w * 8 + s].  They are written by ordinary vector stores of one lane. */
+#define OMNI_DECODE_CUR_LEN 0      /* filled cache positions = the position of the token the next step consumes */
+#define OMNI_DECODE_ROPE_DELTA 1   /* HF's mrope_position_deltas: the RoPE position of that token is cur_len + rope_delta */
+#define OMNI_DECODE_CUR_ID 2       /* the token the next step consumes */
+#define OMNI_DECODE_DONE 3
+#define OMNI_DECODE_N_GENERATED 4
+#define OMNI_DECODE_POS 5          /* scratch of a step: cur_len + rope_delta */
+#define OMNI_DECODE_CTRL_WORDS 8   /* (256 bytes) */
+/* omni_text_penalized_argmax: per sequence s with done == 0 and n_generated < max_new: x[v] = logits[s, v], for seen[s, v] != 0
+ * x < 0 ? x * penalty : x / penalty (HF RepetitionPenaltyLogitsProcessor), t = the LOWEST index of the maximum (a NaN never
+ * wins); then out_tokens[s, n_generated] = t, n_generated += 1, seen[s, t] = 1, cur_id = t, cur_len += 1 (set_len_cu non-null,
+ * the prefill: cur_len = set_len_cu[s + 1] - set_len_cu[s]), done = 1 when t is one of eos_ids or n_generated reached max_new.
+ * A sequence with done != 0 is left untouched.  One workgroup per sequence.
+ * Status: null logits / seen / ctrl / out_tokens, vocab, n_seq or max_new < 1, penalty <= 0, n_eos < 0, ld < vocab,
+ * seen_stride < vocab -> OMNI_ERR_BAD_ARG; n_seq > 8, n_eos > 8 -> OMNI_ERR_UNSUPPORTED. */
+typedef struct omni_penalized_argmax_params {
+  const float* logits;     /* [n_seq, ld] */
+  int64_t ld;
+  uint8_t* seen;           /* [n_seq, seen_stride] */
+  int64_t seen_stride;
+  int32_t* ctrl;           /* the control words */
+  int32_t* out_tokens;     /* [n_seq, max_new] */
+  const int32_t* set_len_cu; /* nullable */
+  int32_t vocab, n_seq, max_new, n_eos;
+  int32_t eos_ids[8];
+  float penalty;
+  int32_t reserved;        /* 0 */
+} omni_penalized_argmax_params;
+extern int (*const omni_text_penalized_argmax)(const omni_penalized_argmax_params* p, omni_stream stream);
+
+/* The decode state: ONE caller-owned device buffer of as many bytes as omni_qwen2_text_decode_state_bytes answers, carved by the library;
+ * `layout` (nullable) receives the byte offsets of the parts a caller reads or writes (cur_id for teacher forcing, done /
+ * n_generated between chunks of steps, out_tokens at the end, the caches in tests). */
+typedef struct omni_text_decode_layout {
+  size_t ctrl;           /* int32 [OMNI_DECODE_CTRL_WORDS][8] */
+  size_t out_tokens;     /* int32 [n_seq][max_new] */
+  size_t seen;           /* uint8 [n_seq][seen_stride]: the tokens of the prompt and of the output so far */
+  size_t seen_stride;
+  size_t k_cache;        /* bf16 [num_layers][n_seq][H_kv][capacity][128], K after RoPE */
+  size_t v_cache;        /* the same for V */
+  size_t logits;         /* fp32 [n_seq][vocab_size]: the last step's logits (where logits_out is null) */
+  size_t qkv;            /* bf16 [n_seq][(H + 2 H_kv) * 128]: the last step's q | k | v row of the LAST layer, after RoPE */
+  size_t total;
+} omni_text_decode_layout;
+/* 0 for weights or counts the decode refuses */
+extern size_t (*const omni_qwen2_text_decode_state_bytes)(const omni_text_weights* w, int32_t n_seq, int32_t capacity,
+                                                          int32_t max_new, omni_text_decode_layout* layout);
+
+typedef struct omni_text_decode_state {
+  int32_t n_seq;               /* sequences, <= 8 */
+  int32_t capacity;            /* cache positions per sequence */
+  int32_t max_new;             /* rows of out_tokens */
+  int32_t n_eos;               /* <= 8 */
+  int32_t eos_ids[8];
+  float repetition_penalty;    /* > 0; 1 = none */
+  int32_t reserved;            /* 0 */
+  const omni_bf16* lm_head;    /* [vocab_size, D] bf16 row-major (untied from embed_tokens in the 7B checkpoint) */
+  void* state;                 /* DEVICE, 16-byte aligned */
+  size_t state_bytes;
+  void* workspace;             /* the prefill's workspace (omni_text_batch_mm.workspace): its error word is the decode's too */
+  size_t workspace_bytes;
+  float* logits_out;           /* nullable: fp32 [n_seq, vocab_size], the raw logits (before the penalty) of the last call */
+} omni_text_decode_state;
+/* omni_qwen2_text_prefill: the driver of omni_qwen2_text_forward_mm - b->out is bit-identical - which also writes every layer's
+ * K (after RoPE) and V rows into the cache, then: logits of each sequence's last row through lm_head, the prompt ids marked in
+ * the seen map, the first token picked (omni_text_penalized_argmax: out_tokens[s, 0], n_generated = 1, EOS test), cur_len = the
+ * prompt's length, rope_delta = max position + 1 - length.  b->n_prompts == st->n_seq, b->max_seqlen <= st->capacity.
+ * omni_qwen2_text_decode_step: one token for every sequence that is not done.  ENQUEUE-ONLY: no host read, no allocation;
+ * position and length are device memory, so any number of steps may be queued back to back.  Per layer: RMSNorm ->
+ * omni_gemv_bf16 q|k|v + bias -> RoPE at cur_len + rope_delta -> K, V appended at cur_len -> omni_decode_attention -> o_proj +
+ * residual -> RMSNorm -> gate|up -> omni_text_swiglu -> down + residual; then final norm -> lm_head (fp32 logits) ->
+ * omni_text_penalized_argmax.  A sequence with done set neither advances nor writes to the cache; cur_len >= capacity or
+ * n_generated >= max_new never writes and sets done, a full cache also the workspace's error word (reported, as always, by
+ * the next omni_qwen2_text_forward* / prefill over that workspace).
+ * Status before any launch (both): null pointer, non-positive count, penalty <= 0, short state or workspace ->
+ * OMNI_ERR_BAD_ARG; n_seq > 8, n_eos > 8, head_dim != 128, more than 8 query heads per K/V head (and whatever
+ * omni_qwen2_text_forward refuses) -> OMNI_ERR_UNSUPPORTED; state, workspace or lm_head not 16-byte aligned -> OMNI_ERR_ALIGN. */
+extern int (*const omni_qwen2_text_prefill)(const omni_text_weights* w, const omni_text_batch_mm* b,
+                                            const omni_text_decode_state* st, omni_stream stream);
+extern int (*const omni_qwen2_text_decode_step)(const omni_text_weights* w, const omni_text_decode_state* st, omni_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * VAE kernels (AutoencoderKLQwenImage.decode — and .encode for the Edit pipelines — for one frame,

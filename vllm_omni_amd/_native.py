@@ -133,6 +133,49 @@ class TextBatchMm(C.Structure):
     ]
 
 
+class GemvParams(C.Structure):
+    """omni_gemv_params: one weight-streaming GEMV of M <= 8 rows (omni_gemv_bf16)."""
+    _fields_ = [
+        ("A", c_bf16_p), ("lda", C.c_int64), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("w_k32_blocked", C.c_int32),
+        ("W", c_bf16_p), ("bias", c_bf16_p), ("res", c_bf16_p), ("ldres", C.c_int64),
+        ("out", c_bf16_p), ("out_f32", c_f32_p), ("ldo", C.c_int64),
+    ]
+
+
+class DecodeAttnParams(C.Structure):
+    """omni_decode_attn_params: one query row per sequence against the KV cache (omni_decode_attention)."""
+    _fields_ = [
+        ("q", c_bf16_p), ("ldq", C.c_int64), ("k_cache", c_bf16_p), ("v_cache", c_bf16_p), ("out", c_bf16_p), ("ldo", C.c_int64),
+        ("lens", c_i32_p), ("done", c_i32_p), ("len_add", C.c_int32), ("n_seq", C.c_int32), ("H", C.c_int32), ("H_kv", C.c_int32),
+        ("head_dim", C.c_int32), ("capacity", C.c_int32), ("softmax_scale", C.c_float), ("reserved", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class PenalizedArgmaxParams(C.Structure):
+    """omni_penalized_argmax_params: repetition penalty + argmax + EOS + the step's bookkeeping (omni_text_penalized_argmax)."""
+    _fields_ = [
+        ("logits", c_f32_p), ("ld", C.c_int64), ("seen", C.c_void_p), ("seen_stride", C.c_int64), ("ctrl", c_i32_p),
+        ("out_tokens", c_i32_p), ("set_len_cu", c_i32_p), ("vocab", C.c_int32), ("n_seq", C.c_int32), ("max_new", C.c_int32),
+        ("n_eos", C.c_int32), ("eos_ids", C.c_int32 * 8), ("penalty", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
+class TextDecodeLayout(C.Structure):
+    """omni_text_decode_layout: byte offsets of the parts of the decode state a caller reads or writes."""
+    _fields_ = [(n, C.c_size_t) for n in ("ctrl", "out_tokens", "seen", "seen_stride", "k_cache", "v_cache", "logits", "qkv", "total")]
+
+
+class TextDecodeState(C.Structure):
+    """omni_text_decode_state: the KV cache and the per-sequence decode words of omni_qwen2_text_prefill / _decode_step."""
+    _fields_ = [
+        ("n_seq", C.c_int32), ("capacity", C.c_int32), ("max_new", C.c_int32), ("n_eos", C.c_int32), ("eos_ids", C.c_int32 * 8),
+        ("repetition_penalty", C.c_float), ("reserved", C.c_int32), ("lm_head", c_bf16_p),
+        ("state", C.c_void_p), ("state_bytes", C.c_size_t), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("logits_out", c_f32_p),
+    ]
+
+
 class VisionLayerWeights(C.Structure):
     """omni_vision_layer_weights: device pointers of one Qwen2.5-VL vision block (padded as the header says)."""
     _fields_ = [(n, c_bf16_p) for n in ("norm1_w", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "gate_up_w", "gate_up_b",
@@ -323,6 +366,14 @@ FEATURE_PROTOTYPES = {
     "omni_text_mrope": (C.c_int, [c_bf16_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_f32_p, c_f32_p, C.c_int32, c_i32_p,
                                   C.POINTER(C.c_int32), c_i32_p, C.c_void_p], 32),
     "omni_qwen2_text_forward_mm": (C.c_int, [C.POINTER(TextWeights), C.POINTER(TextBatchMm), C.c_void_p], 32),
+    "omni_gemv_bf16": (C.c_int, [C.POINTER(GemvParams), C.c_void_p], 64),
+    "omni_decode_attention": (C.c_int, [C.POINTER(DecodeAttnParams), C.c_void_p], 64),
+    "omni_decode_attention_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32], 64),
+    "omni_text_penalized_argmax": (C.c_int, [C.POINTER(PenalizedArgmaxParams), C.c_void_p], 64),
+    "omni_qwen2_text_decode_state_bytes": (C.c_size_t, [C.POINTER(TextWeights), C.c_int32, C.c_int32, C.c_int32,
+                                                        C.POINTER(TextDecodeLayout)], 64),
+    "omni_qwen2_text_prefill": (C.c_int, [C.POINTER(TextWeights), C.POINTER(TextBatchMm), C.POINTER(TextDecodeState), C.c_void_p], 64),
+    "omni_qwen2_text_decode_step": (C.c_int, [C.POINTER(TextWeights), C.POINTER(TextDecodeState), C.c_void_p], 64),
 }
 
 # symbols a library of the SAME ABI version may lack: they were added together with a field that went into former struct
@@ -334,6 +385,10 @@ FEATURE_CFG_EULER_RAGGED = 4                      # OMNI_FEATURE_CFG_EULER_RAGGE
 FEATURE_LORA_MERGE = 8                            # OMNI_FEATURE_LORA_MERGE: omni_lora_merge is exported
 FEATURE_TEXT_ENCODER = 16                         # OMNI_FEATURE_TEXT_ENCODER: omni_qwen2_text_forward and its companions are exported
 FEATURE_VISION_ENCODER = 32                       # OMNI_FEATURE_VISION_ENCODER: omni_qwen2_vision_forward, omni_qwen2_text_forward_mm and companions
+FEATURE_TEXT_DECODE = 64                          # OMNI_FEATURE_TEXT_DECODE: omni_qwen2_text_prefill / _decode_step and their kernels
+DECODE_ATTN_CHUNK = 64                            # OMNI_DECODE_ATTN_CHUNK: keys per workgroup of omni_decode_attention
+DECODE_CUR_LEN, DECODE_ROPE_DELTA, DECODE_CUR_ID, DECODE_DONE, DECODE_N_GENERATED, DECODE_POS = range(6)   # rows of the control words
+DECODE_CTRL_WORDS, DECODE_MAX_SEQ = 8, 8
 ELEM_BF16, ELEM_F16 = 0, 1                        # omni_attn_params.elem_type
 
 _lib = None

@@ -235,5 +235,5 @@ extern "C" int omni_flash_attn_general(const omni_attn_params* p, omni_stream st
 // the version, so a caller has to be able to ask whether the library reads them).
 extern "C" uint32_t omni_features(void) {
   return OMNI_FEATURE_ATTN_F16 | OMNI_FEATURE_TEACACHE_RAGGED | OMNI_FEATURE_CFG_EULER_RAGGED | OMNI_FEATURE_LORA_MERGE |
-         OMNI_FEATURE_TEXT_ENCODER | OMNI_FEATURE_VISION_ENCODER;
+         OMNI_FEATURE_TEXT_ENCODER | OMNI_FEATURE_VISION_ENCODER | OMNI_FEATURE_TEXT_DECODE;
 }

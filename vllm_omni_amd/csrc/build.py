@@ -18,7 +18,7 @@ import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["gemm.hip", "attention.hip", "attention_w64.hip", "attention_general.hip", "attention_sage.hip", "elementwise.hip", "vae.hip", "dit_forward.hip",
-           "lora.hip", "text_forward.hip", "vision_forward.hip"]
+           "lora.hip", "text_forward.hip", "vision_forward.hip", "text_decode.hip"]
 LIB = os.path.join(os.path.dirname(HERE), "libomni_cdna4.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fno-gpu-rdc", "-fvisibility=hidden", "-Wno-unused-result"]

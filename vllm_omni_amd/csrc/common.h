@@ -193,6 +193,22 @@ int omni_internal_teacache_decide(const omni_teacache* tc, const omni_bf16* mod,
 int omni_internal_teacache_post(const omni_teacache* tc, omni_bf16* hidden, const omni_bf16* hidden_in,
                                 const int32_t* cu_seqlens, int32_t n_items, int32_t max_item_rows, int32_t n_img_rows,
                                 int32_t D, void* stream);
+// internal: the KV cache of the greedy decode (text_decode.hip).  The prefill hands text_forward.hip's driver a sink; after
+// each layer's RoPE the driver copies the K and V rows of the fused q|k|v buffer into it (omni_internal_text_kv_write).
+struct omni_text_kv_sink {
+  omni_bf16* k_cache;          // [num_layers][n_seq][H_kv][capacity][128]
+  omni_bf16* v_cache;
+  int32_t n_seq, capacity;
+};
+// rows of qkv -> cache rows of layer `layer`.  cu_seqlens non-null (prefill): row r of sequence s goes to position r - cu[s];
+// null (decode): row s goes to position ctrl[cur_len][s] unless ctrl[done][s].  A position >= capacity is never written.
+int omni_internal_text_kv_write(const omni_bf16* qkv, int64_t ld, int32_t rows, int32_t H, int32_t H_kv,
+                                const omni_text_kv_sink* sink, int32_t layer, const int32_t* cu_seqlens, const int32_t* ctrl,
+                                void* stream);
+// text_forward.hip's one driver, with the sink (null: omni_qwen2_text_forward_mm as it is)
+int omni_internal_text_forward_mm(const omni_text_weights* w, const omni_text_batch_mm* b, const omni_text_kv_sink* sink,
+                                  void* stream);
+int omni_internal_text_check_weights(const omni_text_weights* w);
 // Tuning knobs: the product library reads NOTHING from the process environment and keeps no mutable global state; a build with
 // -DOMNI_DEV (tools/build_variants.sh: same-box A/B runs) reads its knobs through this one function.
 #ifdef OMNI_DEV

@@ -331,7 +331,9 @@ struct TextMm {
 };
 
 // the one driver of both entry points: `b` holds the fields the two batch structs share
-int text_forward_impl(const omni_text_weights* w, const omni_text_batch* b, const TextMm* mm, omni_stream stream) {
+// (`sink`, the prefill of the greedy decode: each layer's K and V rows are also written into the KV cache, after RoPE)
+int text_forward_impl(const omni_text_weights* w, const omni_text_batch* b, const TextMm* mm, omni_stream stream,
+                      const omni_text_kv_sink* sink = nullptr) {
   OMNI_TRY_STATUS(text_check_weights(w));
   if (!b->input_ids || !b->cu_seqlens || !b->out || !b->workspace) return OMNI_ERR_BAD_ARG;
   if (mm) {
@@ -392,6 +394,7 @@ int text_forward_impl(const omni_text_weights* w, const omni_text_batch* b, cons
                                  stream));
     else
       OMNI_TRY_STATUS(text_rope_neox(ws.qkv, Nqkv, R, H, Hkv, w->rope_cos, w->rope_sin, w->rope_npos, b->row_pos, ws.err, stream));
+    if (sink) OMNI_TRY_STATUS(omni_internal_text_kv_write(ws.qkv, Nqkv, R, H, Hkv, sink, l, b->cu_seqlens, nullptr, stream));
     {
       omni_attn_params ap = {};
       ap.q = ws.qkv; ap.k = ws.qkv + Nq; ap.v = ws.qkv + Nq + Hkv * TEXT_HEAD; ap.out = ws.attn;
@@ -425,17 +428,26 @@ int text_forward(const omni_text_weights* w, const omni_text_batch* b, omni_stre
   return text_forward_impl(w, b, nullptr, stream);
 }
 
-int text_forward_mm(const omni_text_weights* w, const omni_text_batch_mm* b, omni_stream stream) {
+int text_forward_mm_sink(const omni_text_weights* w, const omni_text_batch_mm* b, const omni_text_kv_sink* sink, omni_stream stream) {
   if (!b) return OMNI_ERR_BAD_ARG;
   omni_text_batch base = {};
   base.n_prompts = b->n_prompts; base.total_rows = b->total_rows; base.max_seqlen = b->max_seqlen;
   base.input_ids = b->input_ids; base.cu_seqlens = b->cu_seqlens; base.out = b->out;
   base.workspace = b->workspace; base.workspace_bytes = b->workspace_bytes;
   const TextMm mm = {b->row_pos3, b->mrope_section, b->vision_rows, b->vision_row_of, b->n_vision_rows};
-  return text_forward_impl(w, &base, &mm, stream);
+  return text_forward_impl(w, &base, &mm, stream, sink);
+}
+
+int text_forward_mm(const omni_text_weights* w, const omni_text_batch_mm* b, omni_stream stream) {
+  return text_forward_mm_sink(w, b, nullptr, stream);
 }
 
 }  // namespace
+
+int omni_internal_text_forward_mm(const omni_text_weights* w, const omni_text_batch_mm* b, const omni_text_kv_sink* sink, void* stream) {
+  return text_forward_mm_sink(w, b, sink, stream);
+}
+int omni_internal_text_check_weights(const omni_text_weights* w) { return text_check_weights(w); }
 
 // exported as const pointers, not as functions: see the header (the exported functions of ABI v14 are fixed).  Host pass only:
 // a namespace-scope const would otherwise be emitted for the device as well, where its initialiser does not exist

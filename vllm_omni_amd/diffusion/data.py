@@ -160,6 +160,10 @@ class OmniDiffusionConfig:
                                      # omni_qwen2_vision_forward, the language model with M-RoPE in one omni_qwen2_text_forward_mm)
                                      # instead of HF eager.  The text-to-image pipeline (its flag is native_text_encoder) and the
                                      # Layered pipeline (its caption path generates tokens) refuse it at construction
+    native_captioner: bool = False   # NEW, opt-in, Layered pipeline only: the auto-caption of a request without a prompt GENERATES
+                                     # its tokens on this library (NativeQwenCaptioner: vision tower, prefill into a KV cache,
+                                     # greedy decode steps queued without a host round trip per token) instead of HF
+                                     # `generate`.  Layered prompt ENCODING stays HF; every other pipeline refuses the flag
     max_step_tokens: int | None = None  # NEW: admission bound next to max_step_batch — the largest sum of image rows x CFG
                                      # branches one forward may hold (the oldest sample always runs, alone if need be)
     # ---- the reference's remaining fields (data.py:255-360), so that a config written for it constructs here unchanged.

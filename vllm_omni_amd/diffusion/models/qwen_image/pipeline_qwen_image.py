@@ -51,6 +51,7 @@ def get_qwen_image_post_process_func(od_config: OmniDiffusionConfig):
 class QwenImagePipeline(nn.Module):
     _takes_native_vl_encoder = False     # the Edit / Edit-Plus pipelines do
     _native_vl_encoder_hint = "this pipeline's prompts are text only - its flag is native_text_encoder"
+    _takes_native_captioner = False      # the Layered pipeline does: it is the only one that writes a caption
 
     def __init__(self, *, od_config: OmniDiffusionConfig | None = None, prefix: str = "", device=None,
                  transformer: QwenImageTransformer2DModel | None = None, vae: AutoencoderKLQwenImage | None = None,
@@ -61,6 +62,10 @@ class QwenImagePipeline(nn.Module):
         if getattr(self.od_config, "native_vl_encoder", False) and not self._takes_native_vl_encoder:
             raise NotImplementedError(f"{type(self).__name__}: native_vl_encoder=True is the Edit / Edit-Plus prompt encoder (prompts "
                                       "with pictures); " + self._native_vl_encoder_hint)
+        if getattr(self.od_config, "native_captioner", False) and not self._takes_native_captioner:
+            raise NotImplementedError(f"{type(self).__name__}: native_captioner=True is the Layered pipeline's auto-caption (the "
+                                      "one place a Qwen-Image pipeline generates tokens); this pipeline never captions - leave "
+                                      "the flag off")
         dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
         self.device = dev
         self.transformer = transformer if transformer is not None else QwenImageTransformer2DModel(

@@ -17,7 +17,8 @@ Request fields (the reference reads them off the request object, :667-679): `req
 [1, C, H, W] / [1, C, 1, H, W] tensor in [-1, 1] already resized by `preprocess`, or pre-computed `image_latents` +
 `image_latent_grid`), `layers` (default 4), `resolution` (640 | 1024), `cfg_normalize`, `prompt_image`.  An empty prompt asks
 the reference for an auto-caption from its Qwen2.5-VL (`get_image_caption`, :495-516); here that needs a text encoder with a
-`generate` capable model and is otherwise an error that says so."""
+`generate` capable model and is otherwise an error that says so.  Opt-in `OmniDiffusionConfig.native_captioner`: the caption is
+generated on this library (`text_encoder.NativeQwenCaptioner`: KV-cache greedy decode) instead of HF `generate`."""
 from __future__ import annotations
 
 import numpy as np
@@ -69,8 +70,9 @@ def get_qwen_image_layered_pre_process_func(od_config=None):
 class QwenImageLayeredPipeline(QwenImageEditPipeline):
     DEFAULT_LAYERS = 4
     _takes_native_vl_encoder = False
-    _native_vl_encoder_hint = ("the Layered prompt is text only and its auto-caption GENERATES tokens through the HF model, which "
-                               "the native encoder does not do - leave the flag off")
+    _native_vl_encoder_hint = ("the Layered prompt is text only and its auto-caption GENERATES tokens, which the native encoder "
+                               "does not do - leave the flag off (the caption's own flag is native_captioner)")
+    _takes_native_captioner = True
 
     def __init__(self, *, od_config=None, prefix: str = "", device=None, transformer=None, vae=None, **kw):
         tk = dict(kw.pop("transformer_kwargs", None) or {})
@@ -119,24 +121,39 @@ class QwenImageLayeredPipeline(QwenImageEditPipeline):
             from transformers import AutoProcessor
 
             self._caption_processor = AutoProcessor.from_pretrained(pr_dir, local_files_only=True)
+        if getattr(self.od_config, "native_captioner", False):
+            if self._caption_processor is None:
+                raise FileNotFoundError(f"native_captioner=True: {model_dir!r} has no processor/ folder, which the caption needs")
+            from .text_encoder import NativeQwenCaptioner
+
+            # prompt ENCODING stays on the HF model, so its weights are kept (free_source=False); generation settings the decode
+            # does not implement raise here, at load
+            self.captioner = NativeQwenCaptioner.from_hf(self.text_encoder.model, self._caption_processor, free_source=False)
 
     _caption_processor = None
+    caption_max_new_tokens = 512         # reference :508
+    captioner = None                     # a NativeQwenCaptioner (native_captioner=True), used as given
 
     def _encode_text(self, prompts: list[str]):
         return self.text_encoder.get_qwen_prompt_embeds(prompts, device=self.device)
 
     def get_image_caption(self, prompt_image, use_en_prompt: bool = True) -> str:
         """reference :495-516: the text encoder itself writes the prompt when the request has none."""
+        text = IMAGE_CAPTION_PROMPT_EN if use_en_prompt else IMAGE_CAPTION_PROMPT_CN
+        if self.captioner is not None:
+            return self.captioner.generate(text, prompt_image, max_new_tokens=self.caption_max_new_tokens)
+        if getattr(self.od_config, "native_captioner", False):
+            raise NotImplementedError("native_captioner=True but no captioner is loaded (load_text_encoder builds it, or set "
+                                      "`pipeline.captioner`); there is no fall-back to HF generate")
         enc, proc = self.text_encoder, self._caption_processor
         if enc is None or proc is None or not hasattr(getattr(enc, "model", None), "generate"):
             raise NotImplementedError("an empty prompt asks for an auto-caption (reference get_image_caption): that needs the "
                                       "checkpoint's Qwen2.5-VL text encoder AND its processor/ folder; pass a prompt or prompt_embeds")
         from .text_encoder import to_processor_image
 
-        text = IMAGE_CAPTION_PROMPT_EN if use_en_prompt else IMAGE_CAPTION_PROMPT_CN
         dev = next(enc.model.parameters()).device
         inputs = proc(text=text, images=to_processor_image(prompt_image), padding=True, return_tensors="pt").to(dev)
-        ids = enc.model.generate(**inputs, max_new_tokens=512)
+        ids = enc.model.generate(**inputs, max_new_tokens=self.caption_max_new_tokens)
         trimmed = [o[len(i):] for i, o in zip(inputs.input_ids, ids)]
         return proc.batch_decode(trimmed, skip_special_tokens=True, clean_up_tokenization_spaces=False)[0].strip()
 

@@ -13,7 +13,9 @@ Opt-in (`OmniDiffusionConfig.native_text_encoder`): `NativeQwenPromptEncoder` ru
 decoder layers in one `omni_qwen2_text_forward` over the packed valid tokens - with the same tokenizer, template, drop index,
 outputs and mask (text-only prompts).  Opt-in (`OmniDiffusionConfig.native_vl_encoder`): `NativeQwenEditPromptEncoder` does the
 same for the Edit pipelines' prompts WITH pictures - the vision tower in one `omni_qwen2_vision_forward`, the language model with
-real M-RoPE and the image embeddings in the token rows in one `omni_qwen2_text_forward_mm`; the HF Edit encoder stays the default."""
+real M-RoPE and the image embeddings in the token rows in one `omni_qwen2_text_forward_mm`; the HF Edit encoder stays the default.
+Opt-in (`OmniDiffusionConfig.native_captioner`): `NativeQwenCaptioner` GENERATES the Layered pipeline's auto-caption on this library
+- prefill into a KV cache, then greedy decode steps queued without a host round trip per token."""
 from __future__ import annotations
 
 import torch
@@ -799,3 +801,163 @@ class NativeQwenEditPromptEncoder:
                                     vision_row_of=packed[4 * R + n + 1:] if vision_rows is not None else None)
         emb, msk = packed_drop_pad(hidden, lens, drop)
         return emb.to(device=dev, dtype=dtype or self.dtype), msk.to(dev)
+
+
+# ---- the native captioner: greedy decode with a KV cache on this library (the Layered pipeline's auto-caption) -----------------
+CAPTION_DECODE_CHUNK = 16          # decode steps queued between two reads of the stop flags
+CAPTION_CAPACITY_ROUND = 64        # the cache capacity is rounded up to whole key chunks of the decode attention
+# generation settings that would change a greedy result if honoured, with the value at which they do nothing
+_GENERATION_NEUTRAL = dict(num_beam_groups=1, penalty_alpha=None, no_repeat_ngram_size=0, encoder_no_repeat_ngram_size=0,
+                           bad_words_ids=None, force_words_ids=None, constraints=None, forced_bos_token_id=None,
+                           forced_eos_token_id=None, min_length=0, min_new_tokens=None, encoder_repetition_penalty=1.0,
+                           suppress_tokens=None, begin_suppress_tokens=None, sequence_bias=None, guidance_scale=None,
+                           diversity_penalty=0.0, exponential_decay_length_penalty=None, prompt_lookup_num_tokens=None,
+                           renormalize_logits=False, remove_invalid_values=False, dola_layers=None, watermarking_config=None,
+                           stop_strings=None, token_healing=False, max_time=None)
+
+
+def check_generation_config(gc) -> dict:
+    """What the native captioner takes from an HF `generation_config`: {"repetition_penalty", "eos_ids"}.  Greedy search
+    (`num_beams == 1`, `do_sample=False`), or sampling with `top_k == 1` - one survivor, so the result IS the penalised argmax and
+    temperature / top_p cannot change it (what the Qwen2.5-VL instruct checkpoints ship).  A setting is honoured or refused, never
+    ignored: anything else raises NotImplementedError naming the field."""
+    def refuse(field, why):
+        raise NotImplementedError(f"the native captioner does not take generation_config.{field} = {getattr(gc, field, None)!r}: {why}")
+
+    beams = getattr(gc, "num_beams", 1)
+    if beams not in (None, 1):
+        refuse("num_beams", "it decodes greedily, one sequence")
+    if getattr(gc, "do_sample", False):
+        if getattr(gc, "top_k", None) != 1:
+            refuse("top_k", "do_sample=True is taken only with top_k == 1, where one token survives and sampling is the argmax")
+    for field, neutral in _GENERATION_NEUTRAL.items():
+        v = getattr(gc, field, neutral)
+        if v is not None and v != neutral and not (isinstance(v, (list, tuple, dict)) and len(v) == 0):
+            refuse(field, "only repetition_penalty and eos_token_id shape the greedy decode")
+    pen = getattr(gc, "repetition_penalty", None)
+    pen = 1.0 if pen is None else float(pen)
+    if not pen > 0:
+        refuse("repetition_penalty", "it must be positive")
+    eos = getattr(gc, "eos_token_id", None)
+    eos = [] if eos is None else ([int(eos)] if isinstance(eos, int) else [int(e) for e in eos])
+    if len(eos) > 8:
+        refuse("eos_token_id", "at most 8 ids")
+    return dict(repetition_penalty=pen, eos_ids=eos)
+
+
+class NativeQwenCaptioner:
+    """`text_encoder.generate(**inputs, max_new_tokens=...)` of the Layered pipeline's auto-caption on this library: the vision
+    tower (the composed `NativeQwenEditPromptEncoder`), a prefill that fills a KV cache (omni_qwen2_text_prefill) and a greedy
+    decode of one token per omni_qwen2_text_decode_step - steps are queued in chunks with no host round trip per token; between
+    chunks one small read of the stop flags.  Built by `from_hf`; generation settings the decode does not implement raise there."""
+
+    def __init__(self, encoder: "NativeQwenEditPromptEncoder", lm_head: torch.Tensor, generation: dict):
+        from .... import _native as N
+
+        if not N.features() & N.FEATURE_TEXT_DECODE:
+            raise N.OmniNativeError("this libomni_cdna4.so does not report OMNI_FEATURE_TEXT_DECODE: it has no "
+                                    "omni_qwen2_text_prefill / omni_qwen2_text_decode_step - rebuild it (python "
+                                    "vllm_omni_amd/csrc/build.py); the native captioner never falls back to the HF model")
+        vocab, hidden = encoder.text.embed_tokens.shape
+        if tuple(lm_head.shape) != (vocab, hidden) or lm_head.dtype != torch.bfloat16 or not lm_head.is_contiguous():
+            raise ValueError(f"lm_head must be a contiguous bfloat16 [{vocab}, {hidden}] matrix, got {tuple(lm_head.shape)} {lm_head.dtype}")
+        self.encoder, self.lm_head, self.processor = encoder, lm_head, encoder.processor
+        self.repetition_penalty, self.eos_ids = float(generation["repetition_penalty"]), list(generation["eos_ids"])
+        self._state = None
+
+    @classmethod
+    def from_hf(cls, vl_model, processor, free_source: bool = False, generation_config=None, **kw):
+        """From an HF `Qwen2_5_VLForConditionalGeneration` and its processor.  The generation settings come from
+        `vl_model.generation_config` (or `generation_config`) and are checked FIRST: a server fails at load, not at the first
+        empty prompt."""
+        generation = check_generation_config(generation_config if generation_config is not None else vl_model.generation_config)
+        head = getattr(vl_model, "lm_head", None)
+        if head is None or getattr(head, "bias", None) is not None:
+            raise ValueError("the native captioner needs the model's lm_head (a Linear without bias)")
+        lm_head = head.weight.detach().to(torch.bfloat16).contiguous()
+        enc = NativeQwenEditPromptEncoder.from_hf(vl_model, processor, multi_image=False, free_source=free_source, **kw)
+        return cls(enc, lm_head, generation)
+
+    def _inputs(self, text: str, picture):
+        """processor -> vision tower -> the packed prefill batch on the device, as `get_qwen_prompt_embeds` builds it."""
+        enc = self.encoder
+        wdev = enc.text.embed_tokens.device
+        inputs = self.processor(text=[text] if isinstance(text, str) else list(text),
+                                images=None if picture is None else to_processor_image(picture), padding=True, return_tensors="pt")
+        if getattr(inputs, "pixel_values_videos", None) is not None or getattr(inputs, "video_grid_thw", None) is not None:
+            raise ValueError("video inputs: the native captioner takes still pictures only")
+        ids, cu, _, lens = pack_tokens(inputs.input_ids.cpu(), inputs.attention_mask.cpu())
+        if len(lens) != 1:
+            raise ValueError(f"{len(lens)} prompts in one call: the captioner writes one caption per call")
+        vocab = enc.text.embed_tokens.shape[0]
+        if ids.numel() == 0 or int(ids.min()) < 0 or int(ids.max()) >= vocab:
+            raise ValueError(f"token ids outside the embedding table [0, {vocab})")
+        grids, vision_rows, window_index = [], None, None
+        if getattr(inputs, "pixel_values", None) is not None:
+            grids = check_picture_grids(inputs.image_grid_thw, enc.vgeom["merge"])
+            vision_rows, window_index = enc.vision_forward(inputs.pixel_values, grids)
+        row_of = vision_row_map(ids, enc.image_token_id, window_index)
+        pos3 = mrope_positions(ids, lens, enc.image_token_id, grids, enc.vgeom["merge"])
+        R = ids.numel()
+        packed = torch.cat([ids, cu, pos3.reshape(-1), row_of]).to(wdev)                    # one upload
+        return dict(ids=packed[:R], cu=packed[R:R + 2], pos3=packed[R + 2:4 * R + 2].view(3, R), rows=R, max_pos=int(pos3.max()),
+                    vision_rows=vision_rows, vision_row_of=packed[4 * R + 2:] if vision_rows is not None else None,
+                    host_ids=ids)
+
+    def _decode_state(self, rows: int, max_new_tokens: int):
+        from .... import ops
+
+        enc = self.encoder
+        w = enc.text._descriptor()
+        need = ops.qwen2_text_workspace_bytes(w, rows)
+        if enc.text._workspace is None or enc.text._workspace.numel() < need:
+            enc.text._workspace = torch.zeros(need, dtype=torch.uint8, device=self.lm_head.device)   # zeroed: the error word in front
+            self._state = None                                                                   # (it names the workspace)
+        capacity = -(-(rows + max_new_tokens) // CAPTION_CAPACITY_ROUND) * CAPTION_CAPACITY_ROUND
+        st = self._state
+        if st is None or st.capacity < capacity or st.max_new != max_new_tokens:
+            st = self._state = ops.qwen2_decode_state(w, self.lm_head, enc.text._workspace, 1, capacity, max_new_tokens,
+                                                      eos_ids=self.eos_ids, repetition_penalty=self.repetition_penalty)
+        return w, st
+
+    @torch.no_grad()
+    def prefill(self, text: str, picture, max_new_tokens: int = 512):
+        """Vision tower + prefill: -> (weights descriptor, decode state with the first token picked, the prompt's token count)."""
+        from .... import ops
+
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be at least 1")
+        x = self._inputs(text, picture)
+        if x["max_pos"] + max_new_tokens >= self.encoder.text.rope_npos:
+            raise ValueError(f"position {x['max_pos']} + {max_new_tokens} new tokens exceed the RoPE table of "
+                             f"{self.encoder.text.rope_npos} positions")
+        w, st = self._decode_state(x["rows"], max_new_tokens)
+        ops.qwen2_text_prefill(w, st, x["ids"], x["cu"], x["pos3"], self.encoder.mrope_section, x["rows"],
+                               vision_rows=x["vision_rows"], vision_row_of=x["vision_row_of"])
+        return w, st, x["rows"]
+
+    @torch.no_grad()
+    def generate_ids(self, text: str, picture, max_new_tokens: int = 512, chunk: int = CAPTION_DECODE_CHUNK) -> list[int]:
+        """The generated token ids (what HF's `generate` returns behind the prompt), the EOS token included when one ended it."""
+        from .... import _native as N
+        from .... import ops
+
+        w, st, _ = self.prefill(text, picture, max_new_tokens)
+        left = max_new_tokens - 1                                       # the prefill picked the first token
+        while True:
+            flags = st.ctrl[N.DECODE_DONE:N.DECODE_N_GENERATED + 1, :1].cpu()      # the one small read between chunks
+            if int(flags[0, 0]) or left <= 0:
+                break
+            n = min(int(chunk), left)
+            ops.qwen2_text_decode_step(w, st, n)
+            left -= n
+        return st.out_tokens[0, :int(flags[1, 0])].cpu().tolist()
+
+    def generate(self, text: str, picture, max_new_tokens: int = 512, chunk: int = CAPTION_DECODE_CHUNK) -> str:
+        """The caption, decoded exactly as the reference decodes it (pipeline_qwen_image_layered.py:509-513)."""
+        toks = self.generate_ids(text, picture, max_new_tokens, chunk)
+        for i, t in enumerate(toks):
+            if t in self.eos_ids:
+                toks = toks[:i]
+                break
+        return self.processor.batch_decode([toks], skip_special_tokens=True, clean_up_tokenization_spaces=False)[0].strip()

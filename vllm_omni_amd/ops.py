@@ -658,6 +658,170 @@ def qwen2_text_forward_mm(weights: "N.TextWeights", input_ids, cu_seqlens, row_p
     return y
 
 
+# ---- greedy decode with a KV cache (OMNI_FEATURE_TEXT_DECODE) ------------------------------------------------------------------
+def _need_text_decode(what: str) -> None:
+    if not N.features() & N.FEATURE_TEXT_DECODE:
+        raise N.OmniNativeError(f"this libomni_cdna4.so does not report OMNI_FEATURE_TEXT_DECODE: it has no {what} (the native "
+                                "captioner); there is no torch fallback")
+
+
+def gemv_bf16(a, w, bias=None, *, res=None, out=None, out_f32: bool = False, w_k32_blocked: bool = False):
+    """omni_gemv_bf16: a [M <= 8, K] bf16 (a row stride is honoured) times w [N, K] bf16 - row-major or, w_k32_blocked, the
+    K32-blocked order `w_to_k32_blocked` returns - with fp32 accumulation.  bias [N]; res [M, N]: out = res + bf16(a w^T + bias);
+    out_f32: the result is fp32 [M, N] (no res).  `out` may be given (res may alias it)."""
+    _need_text_decode("omni_gemv_bf16")
+    M, K, lda = _rows2d(a, "a")
+    n, kw, ldw = _rows2d(w, "w")
+    if kw != K or ldw != K:
+        raise N.OmniNativeError(f"gemv_bf16: w must be contiguous [N, {K}], got {tuple(w.shape)}")
+    y = out if out is not None else torch.empty(M, n, dtype=torch.float32 if out_f32 else BF16, device=a.device)
+    p = N.GemvParams()
+    p.A, p.lda, p.M, p.N, p.K, p.w_k32_blocked = _p(a, name="a"), lda, M, n, K, int(w_k32_blocked)
+    p.W, p.bias = _p(w, name="w"), _p(bias, name="bias")
+    if res is not None:
+        p.res, p.ldres = _p(res, name="res"), res.stride(0)
+    if out_f32:
+        p.out_f32 = _p(y, torch.float32, "out")
+    else:
+        p.out = _p(y, name="out")
+    p.ldo = y.stride(0)
+    N.check(N.lib().omni_gemv_bf16(C.byref(p), _stream()), "omni_gemv_bf16")
+    return y
+
+
+def decode_attention(q, k_cache, v_cache, lens, *, num_heads: int, len_add: int = 0, done=None, softmax_scale: float | None = None,
+                     out=None):
+    """omni_decode_attention: q [n_seq, >= H * 128] bf16 (one query row per sequence), k_cache / v_cache
+    [n_seq, H_kv, capacity, 128] bf16 contiguous, lens int32 [n_seq] on the device: sequence s attends to its first
+    lens[s] + len_add cache rows.  -> [n_seq, H * 128] bf16.  A sequence with done[s] != 0 is skipped (its row is not written)."""
+    _need_text_decode("omni_decode_attention")
+    n_seq, _, ldq = _rows2d(q, "q")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[0] != n_seq or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise N.OmniNativeError("decode_attention: k_cache / v_cache are contiguous [n_seq, H_kv, capacity, 128] tensors")
+    _, hkv, cap, hd = k_cache.shape
+    y = torch.empty(n_seq, num_heads * 128, dtype=BF16, device=q.device) if out is None else out
+    need = int(N.lib().omni_decode_attention_workspace_bytes(n_seq, num_heads, cap))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
+    p = N.DecodeAttnParams()
+    p.q, p.ldq, p.k_cache, p.v_cache = _p(q, name="q"), ldq, _p(k_cache, name="k_cache"), _p(v_cache, name="v_cache")
+    p.out, p.ldo, p.lens, p.done = _p(y, name="out"), y.stride(0), _p(lens, torch.int32, "lens"), _p(done, torch.int32, "done")
+    p.len_add, p.n_seq, p.H, p.H_kv, p.head_dim, p.capacity = int(len_add), n_seq, int(num_heads), hkv, hd, cap
+    p.softmax_scale = float(softmax_scale if softmax_scale is not None else hd ** -0.5)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+    N.check(N.lib().omni_decode_attention(C.byref(p), _stream()), "omni_decode_attention")
+    return y
+
+
+def penalized_argmax(logits, seen, ctrl, out_tokens, *, penalty: float = 1.0, eos_ids=(), set_len_cu=None):
+    """omni_text_penalized_argmax on logits fp32 [n_seq, vocab], seen uint8 [n_seq, >= vocab], ctrl int32 [8, 8] (the control
+    words, rows N.DECODE_*), out_tokens int32 [n_seq, max_new]: all updated in place."""
+    _need_text_decode("omni_text_penalized_argmax")
+    n_seq, vocab, ld = _rows2d(logits, "logits")
+    if seen.dtype != torch.uint8 or seen.dim() != 2 or seen.stride(1) != 1 or not seen.is_cuda:
+        raise N.OmniNativeError("penalized_argmax: seen is a uint8 [n_seq, >= vocab] DEVICE tensor")
+    if tuple(ctrl.shape) != (N.DECODE_CTRL_WORDS, N.DECODE_MAX_SEQ) or not ctrl.is_contiguous():
+        raise N.OmniNativeError("penalized_argmax: ctrl is a contiguous int32 [8, 8] tensor")
+    if out_tokens.dim() != 2 or not out_tokens.is_contiguous():
+        raise N.OmniNativeError("penalized_argmax: out_tokens is a contiguous int32 [n_seq, max_new] tensor")
+    p = N.PenalizedArgmaxParams()
+    p.logits, p.ld, p.seen, p.seen_stride = _p(logits, torch.float32, "logits"), ld, seen.data_ptr(), seen.stride(0)
+    p.ctrl, p.out_tokens, p.set_len_cu = _p(ctrl, torch.int32, "ctrl"), _p(out_tokens, torch.int32, "out_tokens"), _p(set_len_cu, torch.int32, "set_len_cu")
+    p.vocab, p.n_seq, p.max_new, p.n_eos, p.penalty = vocab, n_seq, out_tokens.shape[1], len(eos_ids), float(penalty)
+    p.eos_ids = (C.c_int32 * 8)(*[int(e) for e in list(eos_ids)[:8]])
+    N.check(N.lib().omni_text_penalized_argmax(C.byref(p), _stream()), "omni_text_penalized_argmax")
+
+
+class Qwen2DecodeState:
+    """The decode state of `qwen2_text_prefill` / `qwen2_text_decode_step`: one device buffer carved by the library, with views of
+    the parts a caller touches - `ctrl` int32 [8, 8] (rows N.DECODE_CUR_LEN .. ), `out_tokens` int32 [n_seq, max_new], `seen`,
+    `k_cache` / `v_cache` bf16 [layers, n_seq, H_kv, capacity, 128], `logits` fp32 [n_seq, vocab] (the raw logits of the last call),
+    `qkv` (the last step's q | k | v rows of the last layer)."""
+
+    def __init__(self, weights: "N.TextWeights", lm_head, workspace, n_seq: int, capacity: int, max_new: int, eos_ids=(),
+                 repetition_penalty: float = 1.0, buffer=None):
+        _need_text_decode("omni_qwen2_text_decode_state_bytes")
+        lay = N.TextDecodeLayout()
+        total = int(N.lib().omni_qwen2_text_decode_state_bytes(C.byref(weights), int(n_seq), int(capacity), int(max_new), C.byref(lay)))
+        if total == 0:
+            raise N.OmniNativeError(f"omni_qwen2_text_decode_state_bytes refuses n_seq {n_seq}, capacity {capacity}, max_new {max_new} "
+                                    "for these weights")
+        if len(eos_ids) > 8:
+            raise N.OmniNativeError(f"{len(eos_ids)} EOS ids: at most 8")
+        dev = lm_head.device
+        if buffer is None:
+            buffer = torch.zeros(total, dtype=torch.uint8, device=dev)
+        elif not buffer.is_cuda or buffer.dtype != torch.uint8 or not buffer.is_contiguous() or buffer.numel() < total:
+            raise N.OmniNativeError(f"the decode state needs a contiguous uint8 DEVICE buffer of {total} bytes")
+        self.buffer, self.state_bytes = buffer, total
+        self.logits = torch.zeros(n_seq, weights.vocab_size, dtype=torch.float32, device=dev)
+        self.layout, self.weights, self.lm_head, self.workspace = lay, weights, lm_head, workspace
+        self.n_seq, self.capacity, self.max_new = int(n_seq), int(capacity), int(max_new)
+        L, hkv = weights.num_layers, weights.num_kv_heads
+        b = self.buffer
+        self.ctrl = b[lay.ctrl:lay.ctrl + 256].view(torch.int32).view(N.DECODE_CTRL_WORDS, N.DECODE_MAX_SEQ)
+        self.out_tokens = b[lay.out_tokens:lay.out_tokens + 4 * n_seq * max_new].view(torch.int32).view(n_seq, max_new)
+        self.seen = b[lay.seen:lay.seen + n_seq * lay.seen_stride].view(n_seq, lay.seen_stride)
+        cache = L * n_seq * hkv * capacity * 128 * 2
+        self.k_cache = b[lay.k_cache:lay.k_cache + cache].view(BF16).view(L, n_seq, hkv, capacity, 128)
+        self.v_cache = b[lay.v_cache:lay.v_cache + cache].view(BF16).view(L, n_seq, hkv, capacity, 128)
+        nqkv = (weights.num_heads + 2 * hkv) * 128
+        self.qkv = b[lay.qkv:lay.qkv + n_seq * nqkv * 2].view(BF16).view(n_seq, nqkv)
+        st = N.TextDecodeState()
+        st.n_seq, st.capacity, st.max_new, st.n_eos = self.n_seq, self.capacity, self.max_new, len(eos_ids)
+        st.eos_ids = (C.c_int32 * 8)(*[int(e) for e in eos_ids])
+        st.repetition_penalty = float(repetition_penalty)
+        st.lm_head = _p(lm_head, name="lm_head")
+        st.state, st.state_bytes = b.data_ptr(), total
+        st.workspace, st.workspace_bytes = workspace.data_ptr(), workspace.numel()
+        st.logits_out = self.logits.data_ptr()
+        self.desc = st
+
+
+def qwen2_decode_state(weights: "N.TextWeights", lm_head, workspace, n_seq: int, capacity: int, max_new: int, eos_ids=(),
+                       repetition_penalty: float = 1.0, buffer=None) -> Qwen2DecodeState:
+    """Allocate (zeroed; or carve the caller's `buffer`) and describe a decode state; `workspace` is the prefill's workspace (its
+    error word is the decode's)."""
+    return Qwen2DecodeState(weights, lm_head, workspace, n_seq, capacity, max_new, eos_ids, repetition_penalty, buffer)
+
+
+def qwen2_text_prefill(weights: "N.TextWeights", state: Qwen2DecodeState, input_ids, cu_seqlens, row_pos3, mrope_section,
+                       max_seqlen: int, vision_rows=None, vision_row_of=None, out=None):
+    """omni_qwen2_text_prefill: `qwen2_text_forward_mm` over `state.workspace` that also fills the KV cache of `state`, computes
+    the logits of every sequence's last row and picks its first token.  -> last hidden state [rows, hidden] bf16."""
+    _need_text_decode("omni_qwen2_text_prefill")
+    rows = input_ids.numel()
+    if tuple(row_pos3.shape) != (3, rows) or not row_pos3.is_contiguous():
+        raise N.OmniNativeError(f"qwen2_text_prefill: row_pos3 must be a contiguous [3, {rows}] tensor, got {tuple(row_pos3.shape)}")
+    if (vision_rows is None) != (vision_row_of is None):
+        raise N.OmniNativeError("qwen2_text_prefill: vision_rows and vision_row_of come together")
+    if vision_rows is not None and (vision_row_of.numel() != rows or not vision_rows.is_contiguous()
+                                    or vision_rows.dim() != 2 or vision_rows.shape[1] != weights.hidden_size):
+        raise N.OmniNativeError(f"qwen2_text_prefill: vision_rows is contiguous [n, {weights.hidden_size}], vision_row_of has "
+                                f"one entry per token ({rows})")
+    y = torch.empty(rows, weights.hidden_size, dtype=BF16, device=input_ids.device) if out is None else out
+    if not y.is_contiguous():
+        raise N.OmniNativeError("qwen2_text_prefill: out must be contiguous")
+    b = N.TextBatchMm()
+    b.n_prompts, b.total_rows, b.max_seqlen = cu_seqlens.numel() - 1, rows, int(max_seqlen)
+    b.input_ids, b.cu_seqlens = _p(input_ids, torch.int32, "input_ids"), _p(cu_seqlens, torch.int32, "cu_seqlens")
+    b.row_pos3, b.out = _p(row_pos3, torch.int32, "row_pos3"), _p(y, name="out")
+    b.workspace, b.workspace_bytes = state.workspace.data_ptr(), state.workspace.numel()
+    if vision_rows is not None:
+        b.vision_rows, b.vision_row_of = _p(vision_rows, name="vision_rows"), _p(vision_row_of, torch.int32, "vision_row_of")
+        b.n_vision_rows = vision_rows.shape[0]
+    b.mrope_section = (C.c_int32 * 3)(*[int(v) for v in mrope_section])
+    N.check(N.lib().omni_qwen2_text_prefill(C.byref(weights), C.byref(b), C.byref(state.desc), _stream()), "omni_qwen2_text_prefill")
+    return y
+
+
+def qwen2_text_decode_step(weights: "N.TextWeights", state: Qwen2DecodeState, steps: int = 1) -> None:
+    """omni_qwen2_text_decode_step, `steps` times back to back: enqueue-only (no host read between them)."""
+    _need_text_decode("omni_qwen2_text_decode_step")
+    fn, s = N.lib().omni_qwen2_text_decode_step, _stream()
+    for _ in range(int(steps)):
+        N.check(fn(C.byref(weights), C.byref(state.desc), s), "omni_qwen2_text_decode_step")
+
+
 def vae_conv2d(x, w, bias=None, *, gamma=None, silu=True, res=None, upsample2x=False, downsample2x=False, clamp=None,
                out=None, x_bordered=False, y_bordered=False, norm_gamma=None, norm_silu=True, keep_raw=True):
     """NHWC bf16 conv (3x3 pad 1 or 1x1): x [B,H,W,Cin], w [Cout,ks,ks,Cin].  downsample2x: the encoder's zero-pad
